@@ -7,12 +7,15 @@ A step = forward + backward + optimizer (clip + RMSprop dense, Adagrad sparse) +
 exchange when N > 1.  Inputs are synthetic Criteo-shape batches generated on the host and made
 resident in HBM before the timed region (a ring of distinct batches is cycled).
 
-Launch: python bench.py --gpus 1 --steps 20 --warmup 5
+Launch: python bench.py --gpus 1 --steps 20 --warmup 5 [--dump-outputs DIR] [--full]
         python -m torch.distributed.run --nproc-per-node N --master-addr 127.0.0.1 bench.py --gpus N
 
-Prints ONE JSON line (rank 0) with the roofline of the dominant kernel (the mixed-parameterisation
-GEMM family, fp32 MFMA) measured with HIP events around its launches inside the timed region, and
-the CPU baseline (oracle/ restatement, torch CPU fp32) timed on this node's host cores.
+A plain run sets up, warms up, times one region of --steps steps, writes the last timed step's
+outputs when --dump-outputs is given, and prints ONE JSON line (rank 0) with the headline figure.
+--full adds what takes runs of its own: the median of three timed regions (--repeats), the roofline
+of the dominant kernel (the mixed-parameterisation GEMM family, fp32 MFMA) measured with HIP events
+around its launches in a pass after the timed region, and the CPU baseline (oracle/ restatement,
+torch CPU fp32) timed on this node's host cores.
 """
 
 import argparse
@@ -45,7 +48,12 @@ def parse():
     ap.add_argument('--config', default='C2')
     ap.add_argument('--batch', type=int, default=0, help='per-GPU batch (default: the config\'s)')
     ap.add_argument('--nbatches', type=int, default=4, help='distinct resident batches cycled')
-    ap.add_argument('--no-cpu-baseline', action='store_true')
+    ap.add_argument('--full', action='store_true',
+                    help='also run the per-kernel HIP-event (roofline) pass and the CPU baseline, and take the median '
+                         'of three timed regions (a plain run times one region and reports the headline figure only)')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help="write what the last timed step's train_step returned as DIR/<name>.npy (float32)")
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='with --full: skip the CPU baseline')
     ap.add_argument('--cpu-batch', type=int, default=0,
                     help="samples per CPU-baseline step (default: the config's per-GPU batch)")
     ap.add_argument('--cpu-steps', type=int, default=2, help='timed CPU-baseline steps (after one warm-up step)')
@@ -56,9 +64,10 @@ def parse():
                          "up within ~100 steps (identical kernel work, but NaN-state operands change kernel timing)")
     ap.add_argument('--allow-nonfinite', action='store_true',
                     help='report instead of failing when a repeat ends on a non-finite loss (diagnostics only)')
-    ap.add_argument('--no-probe', action='store_true', help='skip the per-kernel HIP-event (roofline) pass')
+    ap.add_argument('--no-probe', action='store_true', help='with --full: skip the per-kernel HIP-event (roofline) pass')
     ap.add_argument('--probe-steps', type=int, default=10, help='steps of the roofline pass (0: no roofline)')
-    ap.add_argument('--repeats', type=int, default=3, help='timed regions of --steps steps; value = median')
+    ap.add_argument('--repeats', type=int, default=0,
+                    help='timed regions of --steps steps; value = median (default: 1, with --full 3)')
     ap.add_argument('--no-lookahead', action='store_true',
                     help='row-sharded tables route each step\'s ids when it starts (default: during the step before)')
     ap.add_argument('--no-overlap', action='store_true',
@@ -68,7 +77,10 @@ def parse():
                     help="GEMM / attention arithmetic.  auto: the config's stated precision — C5 (BASELINE "
                          "configs[4]) 'fp8attn' (bf16 GEMMs + block-scaled fp8 attention forward), every other "
                          "config the reference's f32 via the exact split-bf16 GEMMs (ONETRANS_MATMUL overrides)")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.repeats <= 0:
+        args.repeats = 3 if args.full else 1
+    return args
 
 
 def init_dist(args):
@@ -114,6 +126,21 @@ def log(msg):
     """Progress to stderr (rank 0): a long bench keeps writing, and the JSON line stays alone on stdout."""
     if int(os.environ.get('RANK', '0')) == 0:
         print(f'[bench {time.strftime("%H:%M:%S")}] {msg}', file=sys.stderr, flush=True)
+
+
+DUMP_BUDGET_BYTES = 64 << 20       # --dump-outputs: all files together stay under this
+
+
+def dump_outputs(dirname, out):
+    """The tensors train_step returned, as <dirname>/<name>.npy in float32.  An output too large for its share of
+    the budget is written as a fixed, seeded sample of its elements (flat indices in ascending order)."""
+    os.makedirs(dirname, exist_ok=True)
+    share = DUMP_BUDGET_BYTES // max(1, len(out)) // 4 - 64          # float32 elements per file, header room left
+    for name, t in sorted(out.items()):
+        a = t.detach().to(torch.float32).cpu().numpy()
+        if a.size > share:
+            a = a.reshape(-1)[np.sort(np.random.default_rng(0).choice(a.size, size=share, replace=False))]
+        np.save(os.path.join(dirname, name + '.npy'), a)
 
 
 def cpu_baseline(cfg_name, batch, steps, optimizer_config):
@@ -288,6 +315,9 @@ def main():
         route_wait_ranks = allr[:, 2].tolist()
         t = max(per_rank)                             # max over ranks
     loss = float(out['total_loss'].item())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, out)             # the last timed step's return value
+        log(f'outputs written to {args.dump_outputs}')
     trainer.optimizer.exchange_events = None
     for st_ in model.sharded.values():
         st_.events = None
@@ -297,7 +327,7 @@ def main():
     # with the weight-gradient side stream off so each kernel is timed standalone (in the timed region
     # the wgrads overlap the dgrad chain and a launch's duration would include its neighbour's share).
     rep = None
-    if not args.no_probe and args.probe_steps > 0:
+    if args.full and not args.no_probe and args.probe_steps > 0:
         overlap = model.overlap_wgrad
         model.overlap_wgrad = False
         probe = K.Probe()
@@ -457,7 +487,7 @@ def main():
             pmc = attention_pmc(args.config)
             if pmc is not None:
                 res['attention_mfma']['pmc'] = pmc
-    if not args.no_cpu_baseline and world == 1:          # rank 0 at N=1 only
+    if args.full and not args.no_cpu_baseline and world == 1:          # rank 0 at N=1 only
         log('timed region and probe done; CPU baseline')
         res['cpu_baseline'] = cpu_baseline(args.config, args.cpu_batch or B, args.cpu_steps,
                                            cfg.optimizer_config)

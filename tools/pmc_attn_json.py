@@ -1,5 +1,5 @@
 """Summarise the PMC passes of tools/pmc_attn.sh (rocprofv3 --pmc over tools/attn_bench.py at one layer shape) into
-profiles/<round>/pmc_attn_<config>.json, which bench.py reports beside the algorithmic attention fraction.
+profiles/<round>/pmc_attn_<config>.json, which bench.py --full reports beside the algorithmic attention fraction.
 
     python tools/pmc_attn_json.py CONFIG OUT.json gpurun_out/pmc_attn_*/run_counter_collection.csv
 
