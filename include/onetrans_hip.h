@@ -263,6 +263,21 @@ int ot_plane_wide(int on);
  * where K % 256 == N % 256 == 0, else 128 x 256 where N % 256 == 0), 2 = 128 x 256, 3 = 256 x 256; the same slabs
  * bit for bit.  Same switch semantics as ot_plane_wide. */
 int ot_wgrad_wide(int on);
+/* The split-mode pair plane GEMM's epilogue row metadata (output rows, RMSNorm row factors): 1 = loaded once per
+ * tile and parked in LDS (default), 0 = read from the row maps per epilogue row batch.  The same values, so the
+ * same outputs bit for bit.  Process-wide; on = -1 only queries; returns the previous setting. */
+int ot_plane_rowmeta(int on);
+/* The panel form of the split-mode pair plane GEMM (one workgroup walks a row tile's column tiles and copies the
+ * next tile's first stages during the epilogue): 0 = off (default: every launch on the one-tile kernel; the panel
+ * form measured no faster), 1 = auto (pair launches with N >= 256 under the RMSNorm prologue with epilogue 0 /
+ * OT_EPI_BIAS, or plain A with a_rowmax and OT_EPI_GELU_BWD [| OT_EPI_ROWDOT]; launches too small to fill the
+ * device stay on the one-tile kernel), w in 2 .. 64 = on with w column tiles per workgroup, 100 + w = the same on
+ * the four-workgroups-per-CU variant, 200 + w = on the variant that holds A's fragments across the column tiles
+ * (K = 128 only).  Bit-identical outputs.  Process-wide; on = -1 only queries; returns the previous setting. */
+int ot_plane_panel(int on);
+/* Number of GEMM launches that took the panel form since the library was loaded, modulo 2^31 (tests: which kernel
+ * ran). */
+int ot_plane_panel_launches(void);
 int ot_mixed_gemm_rms_img(int mode, const float* A, int64_t lda, int K, const int32_t* in_rows,
                           int a_xform, const float* a_rstd, const float* a_gamma,
                           const float* W, int64_t w_gstride, int64_t ldw, int N,

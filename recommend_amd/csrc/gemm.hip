@@ -110,6 +110,8 @@ struct GemmArgs {
   const float* a_rowmax; int a_rowmax_n;        // split plane GEMM, GELU prologue: A's row maxima (pair arithmetic)
   float* amax_out;                              // vector epilogue: atomic max of |stored output| (pair wgrad bound)
   float* rowabs_out; int rowabs_n;              // vector epilogue: per (out row, column tile) max |stored output|
+  int rowmeta;                                  // pair plane GEMM: row metadata parked in LDS (ot_plane_rowmeta)
+  int panel_w;                                  // panel plane GEMM: column tiles per workgroup
 };
 
 // sum over the 32 lanes that hold one output row in the vector epilogue (same order as the
@@ -192,9 +194,13 @@ __device__ __forceinline__ void store_out4_bf16(uint16_t* dst, f32x4 v) {
 }
 
 // GS: compile the forward stored-GELU path (bf16-mode plane GEMM only: registers elsewhere)
+// rmeta (pair plane GEMM, LAYOUT 1): the tile's 128 output rows and, with ROWSCALE, its 128 row factors (float
+// bits) behind them, parked in LDS by the kernel's prologue — the same values the global row maps give, read
+// without the per-row load -> wait -> dependent load chain (null: read the row maps here).
 template <int EPIT, int LAYOUT, bool ROWSCALE, int RBN = 8, bool GS = false>
 __device__ __forceinline__ void gemm_vec_epilogue(const GemmArgs& p, const f32x16* acc, float* smem, int tm,
-                                                  int n0, int g, int sub = 0, int tid = -1) {
+                                                  int n0, int g, int sub = 0, int tid = -1,
+                                                  const int* rmeta = nullptr) {
   const int epi = EPIT;
   const int t = tid >= 0 ? tid : (int)threadIdx.x, lane = t & 63, wave = t >> 6;
   const int h = lane >> 5, li = lane & 31;
@@ -239,6 +245,11 @@ __device__ __forceinline__ void gemm_vec_epilogue(const GemmArgs& p, const f32x1
       for (int i = 0; i < 8; ++i) {
         const int lr = rb + 8 * i;                      // local row of the half: tile row below
         const int64_t gr = (int64_t)tm * GT + (LAYOUT == 0 ? (lr >> 5) * 64 + 32 * hf + (lr & 31) : 64 * hf + lr);
+        if (LAYOUT == 1 && rmeta) {                     // parked by the kernel's prologue
+          orow[i] = rmeta[64 * hf + lr];
+          if (ROWSCALE) rsc[i] = __int_as_float(rmeta[GT + 64 * hf + lr]);
+          continue;
+        }
         orow[i] = p.out_rows ? p.out_rows[gr] : (int)gr;
         if (ROWSCALE) {                                 // RMSNorm folded into B: scale by the A row's rstd
           const int ir = p.in_rows ? p.in_rows[gr] : (int)gr;
@@ -818,6 +829,12 @@ constexpr int PG_A_BYTES = GT * 16 * 4;            // A stage image: 128 rows x 
 constexpr int PG_B_BYTES = 3 * GT * 16 * 2;        // B stage image: 3 planes x 128 n x 16 bf16
 constexpr int PG_STG_BYTES = PG_A_BYTES + PG_B_BYTES;
 static_assert(64 * (GT + 4) * 4 + 8 * GT * 4 <= 2 * PG_STG_BYTES, "plane GEMM epilogue LDS");
+// TERMS 2 row metadata (128 output rows + 128 row factors): behind the epilogue tile and its dgamma slots, inside
+// the second stage's third-plane KiBs that the two-plane copies never write
+constexpr int PG_META_OFF = 64 * (GT + 4) * 4 + 8 * GT * 4;
+constexpr int PG_META_BYTES = 2 * GT * 4;
+static_assert(PG_META_OFF >= PG_STG_BYTES + PG_A_BYTES + 2 * GT * 16 * 2 && PG_META_OFF + PG_META_BYTES <= 2 * PG_STG_BYTES,
+              "plane GEMM row metadata LDS");
 
 typedef __attribute__((address_space(3))) void lds_void_t;
 
@@ -951,9 +968,16 @@ __global__ __launch_bounds__(256, MINW) void plane_gemm_kernel(GemmArgs p) {
   // it; loaded ahead of the stage copies, so waiting for it does not drain them)
   // (GELU prologue: the row's bound max(max_j a_rowmax, 0.17) >= max |gelu(a)|, from the producer's partial maxima)
   float abound = 1.f;
+  // (not with the GELU prologue: those instantiations sit at the register cap, and their epilogue reads only the
+  // output rows — independent loads, no dependent chain to remove)
+  constexpr bool PMETA = TERMS == 2 && AXT != OT_AX_GELU;
+  int mrow = 0;                                       // row metadata of fragment row ra (TERMS 2, p.rowmeta)
+  bool mok = false;
   if constexpr (TERMS == 2) {
     const int64_t gr = (int64_t)tm * GT + ra;
     int ir = p.in_rows ? p.in_rows[gr] : (int)gr;
+    mok = ir >= 0;
+    if (PMETA && p.rowmeta) mrow = p.out_rows ? p.out_rows[gr] : (int)gr;
     ir = ir < 0 ? 0 : ir;
     if constexpr (AXT == OT_AX_RMSNORM) {
       abound = p.a_rstd[ir];
@@ -967,9 +991,21 @@ __global__ __launch_bounds__(256, MINW) void plane_gemm_kernel(GemmArgs p) {
   if (NSTG >= 3 && nk > 1) issue(1, 1);
   if (NSTG >= 4 && nk > 2) issue(2, 2);
   float asc = 1.f, ainv = 1.f;
+  const int* rmeta = nullptr;
   if constexpr (TERMS == 2) {
     asc = pow2_scale14(AXT == OT_AX_RMSNORM ? sqrtf((float)p.K) / abound : abound);
     ainv = 1.f / asc;
+    // row metadata for the epilogue, one lane per tile row (the lanes of half 0: row ra), parked where neither the
+    // two-plane stage copies nor the epilogue tile reach; the row factor is the rstd this lane holds as abound.
+    // The main loop's barriers (lgkmcnt(0) before each) publish it long before the epilogue reads.
+    if (PMETA && p.rowmeta) {
+      int* rm = reinterpret_cast<int*>(lds + PG_META_OFF);
+      if (h == 0) {
+        rm[ra] = mrow;
+        if (RSC) rm[GT + ra] = __float_as_int(mok ? abound : 0.f);
+      }
+      rmeta = rm;
+    }
   }
   for (int kt = 0; kt < nk; ++kt) {
     // this wave's copies of stage kt are done (with 3 stages the 5 (TERMS 1: 3) of stage kt+1 may
@@ -1054,7 +1090,262 @@ __global__ __launch_bounds__(256, MINW) void plane_gemm_kernel(GemmArgs p) {
   }
   asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
   __syncthreads();                                    // the epilogue reuses the stage buffers
-  gemm_vec_epilogue<EPIT, 1, RSC, MINW >= 4 ? OT_PLANE_EPI_RBN : 8, TERMS == 1>(p, acc, smem, tm, n0, g);
+  gemm_vec_epilogue<EPIT, 1, RSC, MINW >= 4 ? OT_PLANE_EPI_RBN : 8, TERMS == 1>(p, acc, smem, tm, n0, g, 0, -1, rmeta);
+}
+
+// Panel form of the pair plane GEMM (TERMS 2, launches with two or more column tiles): one workgroup owns a row tile
+// and walks `panel_w` of its column tiles.  The row maps, the A source addresses, the A row scale and the epilogue's
+// row metadata are formed once per row tile; a tile's first two stages are copied while the tile before it runs its
+// epilogue.  For that the epilogue keeps out of the stage ring: each wave moves its own 32 rows through a private
+// 8- or 2-row LDS slice in 4 or 16 passes (no workgroup barrier in the epilogue, so nothing drains the copies in flight).
+// One barrier after a tile's last k-step frees the ring for the next tile's first stages.  Every wait on the copies
+// is vmcnt(0) (the two-stage ring waits for all of a stage anyway; at a tile's first k-step that also covers the
+// epilogue stores issued since).  Per output: the same MFMA chain in the same k order, the same unscale and the same
+// epilogue arithmetic as plane_gemm_kernel — bit-identical results.  Measured (profiles/r07/README.md) it does not
+// beat plane_gemm_kernel with the row metadata in LDS, in any variant below: never selected by default.
+constexpr int PP_STG = PG_A_BYTES + 2 * GT * 16 * 2;           // A stage + the pair's two B planes (16 KiB)
+constexpr int PP_CLD = GT + 4;
+constexpr int PP_EPI_OFF = 2 * PP_STG;
+// SR = rows of one wave's epilogue slice: 8 (50,688 B: three workgroups per CU) or 2 (38,016 B: four)
+constexpr int pp_epi_wave(int SR) { return SR * PP_CLD * 4; }
+constexpr int pp_meta_off(int SR) { return PP_EPI_OFF + 4 * pp_epi_wave(SR); }
+constexpr int pp_lds(int SR) { return pp_meta_off(SR) + PG_META_BYTES; }
+static_assert(3 * pp_lds(8) <= 160 * 1024 && 4 * pp_lds(2) <= 160 * 1024, "panel plane GEMM LDS");
+
+// the epilogue of one wave's 32 x 128 block (acc[nb][r]: row (r & 3) + 8 (r >> 2) + 4 h, column 32 nb + li): per pass
+// the wave parks 8 rows in its slice, then each half-wave finishes 4 of them, a float4 column chunk per lane — the
+// lane-to-column layout of gemm_vec_epilogue (the row reductions run over the same 32 lanes in the same order)
+template <int EPIT, bool ROWSCALE, int SR>
+__device__ __forceinline__ void panel_epilogue(const GemmArgs& p, const f32x16* acc, float* ctw, const int* rmeta,
+                                               int row0, int n0, f32x4 bias4, float& am) {
+  static_assert(!(EPIT & ~(OT_EPI_BIAS | OT_EPI_GELU_BWD | OT_EPI_ROWDOT)), "panel plane GEMM epilogue flags");
+  constexpr int epi = EPIT;
+  constexpr bool ROWDOT = (EPIT & OT_EPI_ROWDOT) != 0;
+  const int lane = threadIdx.x & 63, h = lane >> 5, li = lane & 31;
+  const int c4 = li, col = n0 + 4 * c4;
+  const f32x4 rdb4 = bias4;                          // OT_EPI_ROWDOT: the bias subtracted from aux
+  // a pass parks HQ accumulator registers per lane: slice row q + HQ h' holds register HQ j + q of half h'; the
+  // half-wave h then finishes slice rows h + 2 i
+  constexpr int HQ = SR / 2;
+  static_assert(SR == 8 || SR == 2, "panel epilogue slice rows");
+#pragma unroll
+  for (int j = 0; j < 16 / HQ; ++j) {
+#pragma unroll
+    for (int nb = 0; nb < 4; ++nb)
+#pragma unroll
+      for (int q = 0; q < HQ; ++q) ctw[(q + HQ * h) * PP_CLD + 32 * nb + li] = acc[nb][HQ * j + q];
+    int orow[HQ];
+    float rsc[HQ];
+#pragma unroll
+    for (int i = 0; i < HQ; ++i) {
+      const int sr = h + 2 * i, r = HQ * j + sr % HQ;
+      const int tr = row0 + (r & 3) + 8 * (r >> 2) + 4 * (sr / HQ);
+      orow[i] = rmeta[tr];
+      if (ROWSCALE) rsc[i] = __int_as_float(rmeta[GT + tr]);
+    }
+    f32x4 aux4[HQ];
+#pragma unroll
+    for (int i = 0; i < HQ; ++i) {
+      const int64_t o = orow[i] < 0 ? 0 : orow[i];
+      if (epi & OT_EPI_GELU_BWD) aux4[i] = *reinterpret_cast<const f32x4*>(p.aux + o * p.ldaux + col);
+    }
+    // the slice's writes before its reads (LDS runs a wave's accesses in order; this keeps the compiler's order too)
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+#pragma unroll
+    for (int i = 0; i < HQ; ++i) {
+      const int orr = orow[i];
+      f32x4 v = *reinterpret_cast<const f32x4*>(ctw + (h + 2 * i) * PP_CLD + 4 * c4);
+      if (ROWSCALE) v = v * rsc[i];
+      if (epi & OT_EPI_BIAS) v += bias4;
+      if (p.rowmax_out) {                                  // this tile's largest C of the row (signed)
+        float mx = fmaxf(fmaxf(v.x, v.y), fmaxf(v.z, v.w));
+        mx = row32_max(mx);
+        if (orr >= 0 && c4 == 0) p.rowmax_out[(int64_t)orr * p.rowmax_n + n0 / GT] = mx;
+      }
+      if (epi & OT_EPI_GELU_BWD) {
+        v *= gelu_erf_grad4(aux4[i]);
+        if (p.gelu_out && orr >= 0) {                      // the stored GELU (W2 weight gradient's A)
+          const f32x4 hv = gelu_erf4(aux4[i]);
+          store_out4_bf16(p.gelu_out + (int64_t)orr * p.ldgelu + col, hv);
+        }
+        if (ROWDOT) {                                      // this tile's part of sum_f dU_f (U_f - b_f)
+          const f32x4 ub = aux4[i] - rdb4;
+          const float sd = row32_sum(v.x * ub.x + v.y * ub.y + v.z * ub.z + v.w * ub.w);
+          if (orr >= 0 && c4 == 0) p.rowdot[(int64_t)orr * p.rowdot_n + n0 / GT] = sd;
+        }
+      }
+      if (orr >= 0) store_out4(p.C + (int64_t)orr * p.ldc + col, v);
+      if (orr >= 0) am = amax4(am, v);
+      if (p.rowabs_out) {                                  // this tile's max |C| of the row (fp16-pair consumer)
+        float mx = amax4(0.f, v);
+        mx = row32_max(mx);
+        if (orr >= 0 && c4 == 0) p.rowabs_out[(int64_t)orr * p.rowabs_n + n0 / GT] = mx;
+      }
+    }
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");     // the slice is rewritten by the next pass
+  }
+}
+
+// MINW / SR: workgroups per CU and the epilogue slice rows that fit (3 / 8, 4 / 2).  HOLDA (K = 128 only, two
+// workgroups per CU): the row tile's A pair fragments are formed on its first column tile and held in registers (64
+// VGPRs) for the others, which copy only B.
+template <int AXT, int EPIT, int MINW = 3, int SR = 8, bool HOLDA = false>
+__global__ __launch_bounds__(256, MINW) void plane_panel_kernel(GemmArgs p) {
+  static_assert(AXT == OT_AX_RMSNORM || AXT == OT_AX_NONE, "panel plane GEMM prologues");
+  static_assert(MINW * pp_lds(SR) <= 160 * 1024, "panel plane GEMM LDS per CU");
+  constexpr bool RSC = AXT == OT_AX_RMSNORM;
+  extern __shared__ __attribute__((aligned(16))) float smem[];
+  char* lds = reinterpret_cast<char*>(smem);
+  const int pw = p.panel_w, npan = (p.ntn + pw - 1) / pw;
+  const int wg = xcd_remap(blockIdx.x, p.ntm * npan);
+  const int tm = wg / npan, tnb = (wg % npan) * pw;
+  const int tne = tnb + pw < p.ntn ? tnb + pw : p.ntn;
+  const int g = p.tile_group ? p.tile_group[tm] : 0;
+  const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+  const int h = lane >> 5, li = lane & 31;
+  const int nk = p.K >> 4;
+
+  // stage copies as plane_gemm_kernel's (A: wave w's instruction i fills KiB 2w + i of the A image; B: KiB 2w + i of
+  // the two planes); column tile tn's image is nk consecutive 12-KiB blocks
+  const float* asrc[2];
+#pragma unroll
+  for (int i = 0; i < 2; ++i) {
+    const int r = (2 * wave + i) * 16 + (lane >> 2);
+    const int64_t gr = (int64_t)tm * GT + r;
+    int ir = p.in_rows ? p.in_rows[gr] : (int)gr;
+    ir = ir < 0 ? 0 : ir;
+    const int lc = (lane & 3) ^ ((r >> 2) & 3);
+    asrc[i] = p.A + (int64_t)ir * p.lda + 4 * lc;
+  }
+  const int gb = p.w_gstride ? g : 0;
+  const int64_t tstride = (int64_t)nk * PG_B_BYTES;
+  const char* bpan = reinterpret_cast<const char*>(p.bimg) + ((int64_t)gb * p.bimg_ntn + p.bimg_tn0) * tstride;
+  const int blane = 2 * wave * 1024 + 16 * lane;
+  auto issue = [&](int tn, int ks, int buf) {
+    char* sb = lds + buf * PP_STG;
+    const char* bs = bpan + tn * tstride + (int64_t)ks * PG_B_BYTES + blane;
+    if (!HOLDA || tn == tnb) {
+#pragma unroll
+      for (int i = 0; i < 2; ++i)
+        __builtin_amdgcn_global_load_lds((const void*)(asrc[i] + 16 * ks), (lds_void_t*)(sb + (2 * wave + i) * 1024),
+                                         16, 0, 0);
+    }
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+      __builtin_amdgcn_global_load_lds((const void*)(bs + i * 1024),
+                                       (lds_void_t*)(sb + PG_A_BYTES + (2 * wave + i) * 1024), 16, 0, 0);
+  };
+
+  const int ra = 32 * wave + li;                      // this lane's A row (fragment row li)
+  const int aoff0 = ra * 64 + 16 * ((2 * h) ^ ((li >> 2) & 3));
+  const int aoff1 = ra * 64 + 16 * ((2 * h + 1) ^ ((li >> 2) & 3));
+  const int boff = PG_A_BYTES + li * 32 + 16 * (h ^ ((li >> 3) & 1));
+
+  // the row's bound, output row and row factor, once per row tile (plane_gemm_kernel: abound, p.rowmeta)
+  float abound;
+  int mrow;
+  bool mok;
+  {
+    const int64_t gr = (int64_t)tm * GT + ra;
+    int ir = p.in_rows ? p.in_rows[gr] : (int)gr;
+    mok = ir >= 0;
+    mrow = p.out_rows ? p.out_rows[gr] : (int)gr;
+    ir = ir < 0 ? 0 : ir;
+    if constexpr (AXT == OT_AX_RMSNORM) {
+      abound = p.a_rstd[ir];
+    } else {
+      abound = 0.f;
+      for (int j = 0; j < p.a_rowmax_n; ++j) abound = fmaxf(abound, p.a_rowmax[(int64_t)ir * p.a_rowmax_n + j]);
+    }
+  }
+  issue(tnb, 0, 0);
+  if (nk > 1) issue(tnb, 1, 1);
+  const float asc = pow2_scale14(AXT == OT_AX_RMSNORM ? sqrtf((float)p.K) / abound : abound);
+  const float ainv = 1.f / asc;
+  int* rmeta = reinterpret_cast<int*>(lds + pp_meta_off(SR));
+  if (h == 0) {
+    rmeta[ra] = mrow;
+    if (RSC) rmeta[GT + ra] = __float_as_int(mok ? abound : 0.f);
+  }
+  float* ctw = reinterpret_cast<float*>(lds + PP_EPI_OFF + wave * pp_epi_wave(SR));
+  float am = 0.f;
+  u32x4 fah[HOLDA ? 8 : 1][2];
+
+  for (int tn = tnb; tn < tne; ++tn) {
+    // this tile's column scales and form tag (plane 2 of its first unit), back long before the unscale
+    const float* csc = reinterpret_cast<const float*>(bpan + tn * tstride + 2 * GT * 16 * 2);
+    float craw[4];
+#pragma unroll
+    for (int nb = 0; nb < 4; ++nb) craw[nb] = csc[32 * nb + li];
+    uint32_t tag = reinterpret_cast<const uint32_t*>(csc)[GT];
+    // (and its bias chunk: a load inside the epilogue would wait for the next tile's copies issued before it)
+    f32x4 bias4 = {0.f, 0.f, 0.f, 0.f};
+    if (EPIT & (OT_EPI_BIAS | OT_EPI_ROWDOT))
+      bias4 = *reinterpret_cast<const f32x4*>(p.bias + (int64_t)g * p.bias_gstride + tn * GT + 4 * li);
+    f32x16 acc[4];
+#pragma unroll
+    for (int a = 0; a < 4; ++a)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) acc[a][r] = 0.f;
+    auto kstep = [&](int kt) {
+      // stage kt has landed (every wave's after the barrier); the barrier also retires iteration kt - 1's reads of
+      // the buffer that stage kt + 1 then overwrites (stages 0 and 1 were copied ahead of the tile)
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+      __builtin_amdgcn_s_barrier();
+      asm volatile("" ::: "memory");
+      if (kt >= 1 && kt + 1 < nk) issue(tn, kt + 1, (kt + 1) & 1);
+      const char* sb = lds + (kt & 1) * PP_STG;
+      u32x4 fb[4][3];
+#pragma unroll
+      for (int nb = 0; nb < 4; ++nb)
+#pragma unroll
+        for (int q = 0; q < 2; ++q) fb[nb][q] = *reinterpret_cast<const u32x4*>(sb + boff + q * 4096 + nb * 1024);
+      u32x4 fa[3];
+      if (!HOLDA || tn == tnb) {
+        const f32x4 a0 = *reinterpret_cast<const f32x4*>(sb + aoff0);
+        const f32x4 a1 = *reinterpret_cast<const f32x4*>(sb + aoff1);
+        const float av[8] = {a0.x, a0.y, a0.z, a0.w, a1.x, a1.y, a1.z, a1.w};
+        pair8(av, asc, fa);
+        if (HOLDA) { fah[kt][0] = fa[0]; fah[kt][1] = fa[1]; }
+      } else {
+        fa[0] = fah[kt][0]; fa[1] = fah[kt][1];
+      }
+#pragma unroll
+      for (int nb = 0; nb < 4; ++nb) acc[nb] = mfma_pair(fa, fb[nb], acc[nb]);
+    };
+    if constexpr (HOLDA) {                             // (nk == 8: the held fragments are indexed at compile time)
+#pragma unroll
+      for (int kt = 0; kt < 8; ++kt) kstep(kt);
+    } else {
+      for (int kt = 0; kt < nk; ++kt) kstep(kt);
+    }
+    // the scales, the tag and the bias are waited for here, with no copy in flight: the empty statement reads their
+    // registers, so the compiler's wait for those loads stands above it and cannot sink below the next tile's copies
+    // (where it would be a vmcnt(0) that drains them before the epilogue starts)
+    asm volatile("" : "+v"(craw[0]), "+v"(craw[1]), "+v"(craw[2]), "+v"(craw[3]), "+v"(tag), "+v"(bias4));
+    {
+      const float bad = tag == PAIR_IMAGE_TAG ? 1.f : __builtin_nanf("");
+      float cinv[4];
+#pragma unroll
+      for (int nb = 0; nb < 4; ++nb) cinv[nb] = bad / craw[nb];
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        const float ri = __shfl(ainv, (r & 3) + 8 * (r >> 2) + 4 * h, 64);
+#pragma unroll
+        for (int nb = 0; nb < 4; ++nb) acc[nb][r] *= ri * cinv[nb];
+      }
+    }
+    if (tn + 1 < tne) {                                // every wave is past its last stage reads: the ring is free
+      asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
+      __builtin_amdgcn_s_barrier();
+      asm volatile("" ::: "memory");
+      issue(tn + 1, 0, 0);
+      if (nk > 1) issue(tn + 1, 1, 1);
+    }
+    panel_epilogue<EPIT, RSC, SR>(p, acc, ctw, rmeta, 32 * wave, tn * GT, bias4, am);
+  }
+  if (p.amax_out) amax_flush(p.amax_out, am);            // (uniform: every wave reaches it)
 }
 
 // Wide plane GEMM (OT_MATMUL_BF16, N % 256 == 0, K % 32 == 0): the plane GEMM's bf16 form on tiles of 128 rows x
@@ -1626,6 +1917,70 @@ extern "C" int ot_plane_wide(int on) {
   const int prev = g_plane_wide.load();
   if (on >= 0) g_plane_wide.store(on > 4 ? 4 : on);
   return prev;
+}
+
+// The pair plane GEMM's epilogue row metadata (output rows, RMSNorm row factors): 1 = loaded once per tile by one
+// lane per row and parked in LDS (default), 0 = read from the row maps per epilogue row batch; the same values
+#ifndef OT_PLANE_ROWMETA
+#define OT_PLANE_ROWMETA 1
+#endif
+static std::atomic<int> g_plane_rowmeta{OT_PLANE_ROWMETA};
+extern "C" int ot_plane_rowmeta(int on) {
+  const int old = g_plane_rowmeta.load(std::memory_order_relaxed);
+  if (on >= 0) g_plane_rowmeta.store(on ? 1 : 0, std::memory_order_relaxed);
+  return old;
+}
+
+// The panel form of the pair plane GEMM (plane_panel_kernel): 0 = off (default: measured, it does not beat the
+// one-tile kernel with the row metadata in LDS, profiles/r07/README.md), 1 = auto (the pair launches with two or more
+// column tiles whose prologue / epilogue it has; the width by plane_panel_width, which keeps small launches on the
+// one-tile kernel), w in 2 .. 64 = on with w column tiles per workgroup (tests, A/B), 100 + w = the same on the
+// four-workgroups-per-CU variant, 200 + w = on the held-A variant (K = 128; other K: the default variant);
+// bit-identical outputs either way
+#ifndef OT_PLANE_PANEL
+#define OT_PLANE_PANEL 0
+#endif
+static std::atomic<int> g_plane_panel{OT_PLANE_PANEL};
+extern "C" int ot_plane_panel(int on) {
+  const int old = g_plane_panel.load(std::memory_order_relaxed);
+  if (on >= 0) g_plane_panel.store(on > 299 ? 299 : on, std::memory_order_relaxed);
+  return old;
+}
+// launches that took the panel form since the library was loaded (tests: which kernel a launch ran on)
+static std::atomic<long long> g_plane_panel_launches{0};
+extern "C" int ot_plane_panel_launches(void) {
+  return (int)(g_plane_panel_launches.load(std::memory_order_relaxed) & 0x7fffffff);
+}
+// variant 0: three workgroups per CU (8-row epilogue slices); 1: four (2-row slices); 2: two, A fragments held
+static void (*plane_panel_for(int x, int e, int variant))(GemmArgs) {
+#define OT_PANEL_PICK(AX_, EP_)                                                                          \
+  if (x == (AX_) && e == (EP_))                                                                          \
+    return variant == 2 ? plane_panel_kernel<AX_, EP_, 2, 8, true>                                       \
+         : variant == 1 ? plane_panel_kernel<AX_, EP_, 4, 2, false> : plane_panel_kernel<AX_, EP_, 3, 8, false>;
+  OT_PANEL_PICK(OT_AX_RMSNORM, 0)
+  OT_PANEL_PICK(OT_AX_RMSNORM, OT_EPI_BIAS)
+  OT_PANEL_PICK(OT_AX_NONE, OT_EPI_GELU_BWD)
+  OT_PANEL_PICK(OT_AX_NONE, OT_EPI_GELU_BWD | OT_EPI_ROWDOT)
+#undef OT_PANEL_PICK
+  return nullptr;
+}
+// Column tiles per workgroup.  The grid is ntiles x ceil(ntn / width) workgroups on 3 per CU; the last round of
+// resident workgroups may be nearly empty, so the width is halved while the grid has fewer than four rounds (the tail
+// is then at most a quarter of the launch; C2's 4,480 row tiles on 768 slots keep the whole width: 5.8 rounds).
+// 0 (the one-tile kernel) when even two tiles per workgroup leave less than one round of workgroups: a small launch
+// would run its tiles one after another on a few CUs while the others stand idle.
+static int plane_panel_width(int ntiles, int ntn) {
+  static const int slots = [] {
+    int dev = 0, cus = 0;
+    if (hipGetDevice(&dev) != hipSuccess ||
+        hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0)
+      cus = 256;
+    return 3 * cus;
+  }();
+  int w = ntn;
+  while (w > 2 && (int64_t)ntiles * ((ntn + w - 1) / w) < 4 * (int64_t)slots) w = (w + 1) / 2;
+  if ((int64_t)ntiles * ((ntn + w - 1) / w) < slots) return 0;
+  return w;
 }
 
 // the wide kernel for (a_xform, epi), or null; its stage LDS bytes in *stage_lds (opted in above 64 KiB once)
@@ -2975,6 +3330,7 @@ static int mixed_gemm_impl(int mode, const float* A, int64_t lda, int K, const i
   bool plane = false;
   int wide_lds = 0;                     // > 0: the wide / big / square plane GEMM (its stage LDS bytes, its kind)
   int wide_kind = 0;
+  int panel_lds = 0;                    // > 0: the panel form of the pair plane GEMM (its LDS bytes)
   const int e = epi, x = a_xform;
 #define OT_SPEC(NT_, AX_, EP_)                                                                  \
   if (mode == (NT_ ? OT_GEMM_NT : OT_GEMM_NN) && x == AX_ && e == (EP_))                         \
@@ -3059,6 +3415,20 @@ static int mixed_gemm_impl(int mode, const float* A, int64_t lda, int K, const i
     OT_PSPEC_BR(OT_EPI_BIAS | OT_EPI_C_BF16)
 #undef OT_PSPEC_BR
     if (pk) { kern = pk; plane = true; }
+    p.rowmeta = pk && !one ? g_plane_rowmeta.load(std::memory_order_relaxed) : 0;   // (read by the TERMS-2 form)
+    // pair (TERMS 2) launches with two or more column tiles: the panel form where it has the specialisation
+    const bool pair = !one && (x == OT_AX_RMSNORM || (p.a_rowmax && x == OT_AX_NONE));
+    const int pmode = g_plane_panel.load(std::memory_order_relaxed);
+    if (pk && pair && p.ntn >= 2 && pmode) {
+      const int pvar = pmode >= 200 ? (K == 128 ? 2 : 0) : pmode >= 100 ? 1 : 0;
+      const int pwid = pmode == 1 ? plane_panel_width(ntiles, p.ntn) : std::min(std::max(pmode % 100, 2), (int)p.ntn);
+      void (*ppk)(GemmArgs) = pwid > 0 ? plane_panel_for(x, e, pvar) : nullptr;
+      if (ppk) {
+        kern = ppk;
+        p.panel_w = pwid;
+        panel_lds = pp_lds(pvar == 1 ? 2 : 8);
+      }
+    }
     // bf16 mode, whole 256-column tiles and 32-k stages: the wide tile (same outputs)
     // tile: 1 auto, 2 / 3 / 4 force 128 x 256 / 128 x 512 / 256 x 256 (where the shape allows it)
     const int wmode = g_plane_wide.load(std::memory_order_relaxed);
@@ -3138,6 +3508,10 @@ static int mixed_gemm_impl(int mode, const float* A, int64_t lda, int K, const i
     const unsigned wg = wide_kind == 3 ? (unsigned)(ntiles / 2) * (unsigned)(N / PW_COLS)
                                        : (unsigned)ntiles * (unsigned)(N / (wide_kind == 2 ? PB_COLS : PW_COLS));
     hipLaunchKernelGGL(kern, dim3(wg), dim3(wide_kind == 3 ? 512 : 256), wshm, s, p);
+  } else if (p.panel_w > 0) {
+    const unsigned npan = (unsigned)((p.ntn + p.panel_w - 1) / p.panel_w);
+    hipLaunchKernelGGL(kern, dim3((unsigned)ntiles * npan), dim3(256), (size_t)panel_lds, s, p);
+    g_plane_panel_launches.fetch_add(1, std::memory_order_relaxed);
   } else {
     hipLaunchKernelGGL(kern, dim3(nwg), dim3(256), launch_shmem, s, p);
   }

@@ -353,6 +353,25 @@ def wgrad_wide(on: int = -1) -> int:
     return _lib.size('ot_wgrad_wide', int(on))
 
 
+def plane_rowmeta(on: int = -1) -> int:
+    """ot_plane_rowmeta: the pair plane GEMM's epilogue row metadata — 1: parked in LDS once per tile (default), 0:
+    read from the row maps per row batch — or query (-1); returns the previous setting (bit-identical outputs)."""
+    return _lib.size('ot_plane_rowmeta', int(on))
+
+
+def plane_panel(on: int = -1) -> int:
+    """ot_plane_panel: the panel form of the pair plane GEMM (one workgroup per row tile walks its column tiles) — 0:
+    off (default), 1: auto, w in 2 .. 64: w column tiles per workgroup, 100 + w: the four-workgroups-per-CU variant,
+    200 + w: A's fragments held across the column tiles (K = 128) — or query (-1); returns the previous setting
+    (bit-identical outputs)."""
+    return _lib.size('ot_plane_panel', int(on))
+
+
+def plane_panel_launches() -> int:
+    """ot_plane_panel_launches: GEMM launches that took the panel form since the library was loaded."""
+    return _lib.size('ot_plane_panel_launches')
+
+
 def split_images(base, desc_dev, ndesc, total_units, img) -> None:
     call('ot_split_images', ptr(base), ptr(desc_dev), ndesc, total_units, ptr(img), _prec(), stream())
 
