@@ -584,6 +584,32 @@ int ot_clip_rmsprop(float* w, float* g, float* v, float* m, const int64_t* segs_
                     int64_t max_seg_elems, float lr, float rho, float eps, float momentum, float clip,
                     void* workspace, size_t ws_bytes, void* stream);
 
+/* ---- streaming metrics (metrics.hip) -------------------------------------------------------
+ * The running Keras metrics the reference updates in every train / validation step (train.py:95-109,
+ * 140-150, 176-185; evaluate.py:39-56) as additive device state, updated by one stream-ordered call:
+ * no sync, no allocation, graph-capturable.  The caller zeroes the state to reset it and finalises
+ * the metrics on the host (recommend_amd/metrics.py).
+ *   probs, labels  task t's B values at + t * task_stride (the [T, B] layout of the model's
+ *                  probabilities and of the stacked labels); task_stride >= B; any float alignment
+ *                  (16-byte vector loads when both rows allow them, scalar loads otherwise: the
+ *                  result does not depend on which)
+ *   bounds         nb thresholds, ascending, doubles, device memory; 1 <= nb <= 1024
+ *   counts         [T][2][nb+1] int64, += : class = (label > 0.5); bin = the number of j with
+ *                  (double)p > bounds[j] (strict, as Keras's pred > threshold; a NaN is greater
+ *                  than nothing: bin 0).  Exact: a per-workgroup LDS histogram, its non-zero
+ *                  bins flushed with 64-bit integer atomics.
+ *   sums           [T][4] double, += : {n, sum (p-y)^2, sum |p-y|, sum bce}, each term in double
+ *                  from the f32 inputs; bce = -(y log(c+1e-7) + (1-y) log(1-c+1e-7)),
+ *                  c = p clipped to [1e-7, 1-1e-7] (tf.keras.losses.BinaryCrossentropy on
+ *                  probabilities).  Bit-reproducible: fixed-order reduction inside a workgroup,
+ *                  workgroup partials folded in index order through the workspace; no float
+ *                  atomics.
+ * Every task gets every statistic (the host picks what it reports).  T <= 32, B >= 1. */
+size_t ot_metrics_workspace_size(int T, int B);
+int ot_metrics_update(const float* probs, const float* labels, int T, int B, int64_t task_stride,
+                      const double* bounds, int nb, int64_t* counts, double* sums, void* workspace,
+                      size_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -10,7 +10,7 @@ __version__ = '1.0.0'
 from .config import OneTransConfig, get_model_config, workload_config  # noqa: F401
 from .data import create_sample_batch, criteo_batch, make_batch  # noqa: F401
 from .features import DataLoader, FeatureProcessor, OneTransDataset, SequenceProcessor  # noqa: F401
-from .metrics import auc, keras_auc  # noqa: F401
+from .metrics import StreamingMetrics, auc, keras_auc  # noqa: F401
 
 
 def __getattr__(name):
@@ -21,8 +21,12 @@ def __getattr__(name):
     if name in ('OneTransTrainer', 'train_one_trans_model', 'OneTransOptimizer'):
         from . import trainer
         return getattr(trainer, name)
+    if name in ('OneTransEvaluator', 'load_model_for_evaluation'):
+        from . import evaluate
+        return getattr(evaluate, name)
     raise AttributeError(name)
 
 
 __all__ = ['OneTransModel', 'OneTransConfig', 'get_model_config', 'DataLoader', 'FeatureProcessor',
-           'SequenceProcessor', 'OneTransDataset', 'OneTransTrainer', 'train_one_trans_model', 'create_sample_batch', 'criteo_batch', 'make_batch', 'workload_config', 'auc', 'keras_auc']
+           'SequenceProcessor', 'OneTransDataset', 'OneTransTrainer', 'train_one_trans_model', 'create_sample_batch', 'criteo_batch', 'make_batch', 'workload_config', 'auc', 'keras_auc',
+           'StreamingMetrics', 'OneTransEvaluator', 'load_model_for_evaluation']

@@ -571,6 +571,17 @@ def bce_bwd(probs, labels, gscale, T, B, dprobs, mse_mask: int = 0) -> None:
         _probe.end('head_loss', 0.0, ev)
 
 
+def metrics_update(probs, labels, T, B, task_stride, bounds, nb, counts, sums, device=None) -> None:
+    """Streaming metric state += this batch (train.py:140-150): ``counts`` [T, 2, nb+1] int64 (class x bin
+    over the ``nb`` ascending float64 ``bounds``), ``sums`` [T, 4] float64 {n, Σ(p-y)², Σ|p-y|, Σ bce}."""
+    ws = workspace(size('ot_metrics_workspace_size', T, B), device)
+    ev = _probe.begin() if _probe is not None else None
+    call('ot_metrics_update', ptr(probs), ptr(labels), T, B, task_stride, ptr(bounds), nb, ptr(counts), ptr(sums),
+         ptr(ws), ws.numel(), stream())
+    if ev is not None:
+        _probe.end('metrics', 0.0, ev)
+
+
 def task_loss_logits_fwd(logits, probs, labels, T, B, loss, device=None, mse_mask: int = 0) -> None:
     """Σ_task loss (train.py:78-93) as Keras 2.12 computes it on sigmoid heads: BCE from the logits, MSE
     (bits of ``mse_mask``) from the probabilities."""

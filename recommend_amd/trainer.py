@@ -24,7 +24,7 @@ import torch
 from . import dist as otdist
 from . import kernels as K
 from .config import OneTransConfig, get_model_config
-from .metrics import auc, keras_auc
+from .metrics import StreamingMetrics, auc, keras_auc
 from .model import BINARY_TASKS, OneTransModel, keras_bce_loss
 
 
@@ -310,6 +310,23 @@ class OneTransTrainer:
         self.device = self.model.flat.device
         self.optimizer = OneTransOptimizer(self.model, config)
         self.history = {'train_loss': [], 'val_loss': [], 'train_metrics': {}, 'val_metrics': {}}
+        # the reference's running per-step metrics (train.py:95-109), off unless enable_metrics() / fit()
+        self.train_metrics: Optional[StreamingMetrics] = None
+        self.val_metrics: Optional[StreamingMetrics] = None
+
+    def enable_metrics(self, num_thresholds: int = 200) -> None:
+        """Create the running train / validation metric states (train.py:53-54, 95-109): from here on every
+        ``train_step`` / ``val_step`` adds its batch to them with one stream-ordered launch (no host sync; the
+        weights do not depend on it).  Off by default: the steps then launch exactly what they always did."""
+        self.train_metrics = StreamingMetrics(self.config.tasks, self.device, num_thresholds)
+        self.val_metrics = StreamingMetrics(self.config.tasks, self.device, num_thresholds)
+
+    def metric_results(self, metrics: StreamingMetrics, extended: bool = False) -> Dict[str, float]:
+        """``metrics.result()`` over all ranks: in a data-parallel run the state is summed over the ranks first
+        (in place, as Keras aggregates metric variables under a distribution strategy)."""
+        if otdist.world() > 1:
+            metrics.all_reduce()
+        return metrics.result(extended)
 
     # --------------------------------------------------------------- steps
     def train_step(self, batch_data, next_batch=None) -> Dict[str, torch.Tensor]:
@@ -328,6 +345,8 @@ class OneTransTrainer:
         self.optimizer.begin_backward()
         loss.backward()
         self.optimizer.step()
+        if self.train_metrics is not None:               # train.py:140-150
+            self.train_metrics.update(y, probs.detach())
         return {'total_loss': loss.detach(), 'probs': probs.detach()}
 
     @torch.no_grad()
@@ -338,6 +357,8 @@ class OneTransTrainer:
         y = labels if isinstance(labels, torch.Tensor) else stack_labels(labels, self.config.tasks, dev)
         probs = self.model.forward_probs(_to_dev(non_seq, dev), _seq_inputs(self.model, seq, dev), training=False)
         loss = keras_bce_loss(y, probs, self.config.tasks, label_rank(labels))
+        if self.val_metrics is not None:                 # train.py:176-185
+            self.val_metrics.update(y, probs)
         return {'total_loss': loss, 'probs': probs}
 
     def evaluate(self, batches) -> Dict[str, float]:
@@ -370,6 +391,59 @@ class OneTransTrainer:
             if val_batches:
                 self.history['val_metrics'][ep] = self.evaluate(val_batches)
             print(f'epoch {ep + 1}/{epochs} loss {self.history["train_loss"][-1]:.5f} ({time.time() - t0:.1f}s)')
+        return self.history
+
+    def fit(self, train_batches, val_batches=None, epochs: int = 10, save_freq: int = 1,
+            early_stopping_patience: int = 5) -> Dict:
+        """The reference's training loop (train.py:192-279).  Per epoch: the training steps, then the validation
+        steps; ``history['train_loss' / 'val_loss']`` get the epoch means (the validation loss is the training
+        loss without validation data) and ``history['train_metrics' / 'val_metrics'][epoch]`` the running
+        metrics' results; then ``best_model`` on a strict improvement of the validation loss, ``model_epoch_{n}``
+        every ``save_freq`` epochs, the early stop after ``early_stopping_patience`` epochs without improvement,
+        and the reset of both metric states.  ``final_model`` is saved after the loop.  The per-step losses and
+        the metric states stay on the device; each is read once per epoch."""
+        if getattr(self, 'train_metrics', None) is None or getattr(self, 'val_metrics', None) is None:
+            self.enable_metrics()
+
+        def epoch_mean(losses) -> float:
+            # one read of the stacked device scalars; in a data-parallel run the mean over the ranks, so every
+            # rank takes the same checkpoint / early-stop decisions
+            m = torch.stack(losses).mean()
+            if otdist.world() > 1:
+                m = m.clone()
+                otdist.allreduce_sum_async(m).wait()
+                m = m / otdist.world()
+            return float(m)
+
+        best_val_loss, patience_counter = float('inf'), 0
+        for epoch in range(epochs):
+            t0 = time.time()
+            losses = [self.train_step(b)['total_loss'] for b in train_batches]
+            avg_train_loss = epoch_mean(losses)
+            if val_batches:
+                losses = [self.val_step(b)['total_loss'] for b in val_batches]
+                avg_val_loss = epoch_mean(losses)
+            else:
+                avg_val_loss = avg_train_loss
+            self.history['train_loss'].append(avg_train_loss)
+            self.history['val_loss'].append(avg_val_loss)
+            self.history['train_metrics'][epoch] = self.metric_results(self.train_metrics)
+            self.history['val_metrics'][epoch] = self.metric_results(self.val_metrics)
+            print(f'epoch {epoch + 1}/{epochs} - train loss {avg_train_loss:.4f}, val loss {avg_val_loss:.4f} '
+                  f'({time.time() - t0:.2f}s)')
+            if avg_val_loss < best_val_loss:
+                best_val_loss, patience_counter = avg_val_loss, 0
+                self.save_model('best_model')
+            else:
+                patience_counter += 1
+            if (epoch + 1) % save_freq == 0:
+                self.save_model(f'model_epoch_{epoch + 1}')
+            if patience_counter >= early_stopping_patience:
+                print(f'early stop at epoch {epoch + 1}')
+                break
+            self.train_metrics.reset_states()
+            self.val_metrics.reset_states()
+        self.save_model('final_model')
         return self.history
 
     # --------------------------------------------------------------- checkpoint (train.py:281-338)
