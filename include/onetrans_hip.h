@@ -583,6 +583,16 @@ size_t ot_clip_rmsprop_workspace_size(int nseg, int64_t max_seg_elems);
 int ot_clip_rmsprop(float* w, float* g, float* v, float* m, const int64_t* segs_dev, int nseg,
                     int64_t max_seg_elems, float lr, float rho, float eps, float momentum, float clip,
                     void* workspace, size_t ws_bytes, void* stream);
+/* The same clip over the same segments, then Keras-2.12 Adam (train.py:57-63; 71-74 with the Keras defaults):
+ *   alpha = lr sqrt(1 - beta2^step) / (1 - beta1^step)      (host, double)
+ *   m += (g - m)(1 - beta1); v += (g^2 - v)(1 - beta2); w -= (m alpha) / (sqrt(v) + eps)
+ * eps is outside the square root (RMSprop above: inside).  step >= 1 is the index of the step being applied
+ * (Keras' iterations + 1); 0 <= beta1 < 1; 0 <= beta2 <= 1 (beta2 == 1: alpha = 0, w and v keep their bits, m
+ * moves).  Elements outside every segment are not touched.  No host sync; deterministic. */
+size_t ot_clip_adam_workspace_size(int nseg, int64_t max_seg_elems);
+int ot_clip_adam(float* w, float* g, float* m, float* v, const int64_t* segs_dev, int nseg,
+                 int64_t max_seg_elems, float lr, float beta1, float beta2, float eps, int64_t step, float clip,
+                 void* workspace, size_t ws_bytes, void* stream);
 
 /* ---- streaming metrics (metrics.hip) -------------------------------------------------------
  * The running Keras metrics the reference updates in every train / validation step (train.py:95-109,

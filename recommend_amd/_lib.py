@@ -148,6 +148,9 @@ SIGNATURES = {
     'ot_clip_rmsprop_workspace_size': (c_size_t, [c_int, I64]),
     'ot_clip_rmsprop': (c_int, [P, P, P, P, P, c_int, I64, c_float, c_float, c_float, c_float, c_float, P,
                                 c_size_t, P]),
+    'ot_clip_adam_workspace_size': (c_size_t, [c_int, I64]),
+    'ot_clip_adam': (c_int, [P, P, P, P, P, c_int, I64, c_float, c_float, c_float, c_float, I64, c_float, P,
+                             c_size_t, P]),
     'ot_metrics_workspace_size': (c_size_t, [c_int, c_int]),
     'ot_metrics_update': (c_int, [P, P, c_int, c_int, I64, P, c_int, P, P, P, c_size_t, P]),
 }

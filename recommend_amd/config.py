@@ -31,7 +31,7 @@ from __future__ import annotations
 
 import copy
 import math
-from typing import Dict, List, Optional
+from typing import Dict, List, Optional, Tuple
 
 
 class OneTransConfig:
@@ -216,6 +216,33 @@ def get_model_config(model_type: str = 'default') -> OneTransConfig:
     return config_map[model_type]()
 
 
+def dense_optimizer_spec(config: OneTransConfig) -> Tuple[str, Dict[str, float]]:
+    """The dense optimizer ``optimizer_config['dense_optimizer']`` selects, as the reference's
+    ``_create_optimizer`` does (train.py:53-76): ``(kind, params)``.
+
+    * ``'rmsprop'``: Keras RMSprop — ``{lr, rho, eps, momentum}`` (rho / eps: ``rmsprop_rho`` /
+      ``rmsprop_epsilon``; momentum: ``optimizer_config['momentum']``, 0 without it).
+    * ``'adam'``: Keras Adam — ``{lr, beta1, beta2, eps}`` from ``optimizer_config['beta1' / 'beta2' /
+      'epsilon']``, 0.9 / 0.999 / 1e-8 without them (train.py:60-62).
+    * any other name, or none: the reference falls back to ``tf.keras.optimizers.Adam`` with only the
+      learning rate given (train.py:71-74), i.e. the Keras defaults beta1 0.9, beta2 0.999, epsilon 1e-7;
+      ``beta1`` / ``beta2`` / ``epsilon`` of ``optimizer_config`` are not read on this branch.
+
+    ``lr`` is ``optimizer_config['dense_lr']``, else ``config.learning_rate``.  (The reference reads
+    ``optimizer_config['learning_rate']``, a key its own default dict does not have, so it raises KeyError on its
+    own defaults; that key is not read here.)"""
+    oc = config.optimizer_config
+    lr = float(oc.get('dense_lr', config.learning_rate))
+    name = oc.get('dense_optimizer')
+    if name == 'rmsprop':
+        return 'rmsprop', {'lr': lr, 'rho': float(config.rmsprop_rho), 'eps': float(config.rmsprop_epsilon),
+                           'momentum': float(oc.get('momentum', 0.0))}
+    if name == 'adam':
+        return 'adam', {'lr': lr, 'beta1': float(oc.get('beta1', 0.9)), 'beta2': float(oc.get('beta2', 0.999)),
+                        'eps': float(oc.get('epsilon', 1e-8))}
+    return 'adam', {'lr': lr, 'beta1': 0.9, 'beta2': 0.999, 'eps': 1e-7}
+
+
 DEFAULT_CONFIG = OneTransConfig()
 
 # ---------------------------------------------------------------------------
@@ -311,5 +338,5 @@ def algorithmic_flops_per_sample(cfg: OneTransConfig, seq_lens: List[int], f_ns:
 
 
 __all__ = ['OneTransConfig', 'OneTransSmallConfig', 'OneTransLargeConfig', 'get_model_config',
-           'DEFAULT_CONFIG', 'workload_config', 'algorithmic_flops_per_sample',
+           'dense_optimizer_spec', 'DEFAULT_CONFIG', 'workload_config', 'algorithmic_flops_per_sample',
            'CRITEO_CARDINALITIES']

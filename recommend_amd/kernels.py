@@ -682,3 +682,13 @@ def clip_rmsprop(w, g, v, m, segs_dev, nseg, max_seg, lr, rho, eps, momentum, cl
          float(eps), float(momentum), float(clip), ptr(ws), ws.numel(), stream())
     if ev is not None:
         _probe.end('optimizer', 0.0, ev)
+
+
+def clip_adam(w, g, m, v, segs_dev, nseg, max_seg, lr, beta1, beta2, eps, step, clip, device=None) -> None:
+    """Per-segment clip + Keras Adam (ot_clip_adam); ``step`` is the 1-based index of the step being applied."""
+    ws = workspace(size('ot_clip_adam_workspace_size', nseg, max_seg), device)
+    ev = _probe.begin() if _probe is not None else None
+    call('ot_clip_adam', ptr(w), ptr(g), ptr(m), ptr(v), ptr(segs_dev), nseg, max_seg, float(lr), float(beta1),
+         float(beta2), float(eps), int(step), float(clip), ptr(ws), ws.numel(), stream())
+    if ev is not None:
+        _probe.end('optimizer', 0.0, ev)

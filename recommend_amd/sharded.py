@@ -248,12 +248,14 @@ class ShardedTable:
         if ev0 is not None:
             self.events.append((ev0, self._mark()))
 
-    def full_table(self) -> torch.Tensor:
-        """Gather the logical table on every rank (tests / checkpoints of small tables)."""
+    def full_table(self, shard: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """Gather the logical table on every rank (tests / checkpoints of small tables); ``shard``: another
+        tensor laid out like this rank's shard (the table's Adagrad accumulator) to gather instead."""
+        shard = self.table if shard is None else shard
         if self.world == 1:
-            return self.table[:self.local_rows].clone()
+            return shard[:self.local_rows].clone()
         gloo = dist.get_backend() == 'gloo'
-        src = self.table.cpu() if gloo else self.table
+        src = shard.cpu() if gloo else shard
         parts = [torch.empty_like(src) for _ in range(self.world)]
         dist.all_gather(parts, src)
         parts = [q.to(self.device) for q in parts]

@@ -2,7 +2,8 @@
 
 ``train_step`` is the metric's "fwd+bwd" unit (train.py:111-155): forward (tuple call
 convention, train.py:118) -> Σ_task Keras BCE (train.py:124-128) -> backward (train.py:131) ->
-per-variable clip_by_norm (train.py:134-135) -> RMSprop(momentum) (train.py:138) -> sparse Adagrad
+per-variable clip_by_norm (train.py:134-135) -> RMSprop(momentum) or Adam, whichever
+``optimizer_config['dense_optimizer']`` selects (train.py:53-76, 138) -> sparse Adagrad
 on the embedding rows touched (build extension).  Defect D5 mapping: the trainer reads
 ``gradient_clip_norm`` (the reference reads the absent ``gradient_clip``) and
 ``optimizer_config['dense_lr']`` (the reference reads the absent ``learning_rate``); mixed
@@ -23,7 +24,7 @@ import torch
 
 from . import dist as otdist
 from . import kernels as K
-from .config import OneTransConfig, get_model_config
+from .config import OneTransConfig, dense_optimizer_spec, get_model_config
 from .metrics import StreamingMetrics, auc, keras_auc
 from .model import BINARY_TASKS, OneTransModel, keras_bce_loss
 
@@ -59,21 +60,26 @@ def stack_labels(labels: Dict, tasks, dev) -> torch.Tensor:
 
 
 class OneTransOptimizer:
-    """Dense: clip_by_norm per reference variable + Keras RMSprop(momentum) on the flat buffer,
-    one fused multi-segment launch (ot_clip_rmsprop).  Sparse: Keras Adagrad on the de-duplicated
-    rows of each embedding table (ot_sparse_adagrad)."""
+    """Dense: clip_by_norm per reference variable + the optimizer ``optimizer_config['dense_optimizer']`` names
+    (config.dense_optimizer_spec, train.py:53-76) on the flat buffer, one fused multi-segment call: Keras
+    RMSprop(momentum) (ot_clip_rmsprop) or Keras Adam (ot_clip_adam).  Both keep two flat state buffers: ``v`` and
+    ``m`` (RMSprop: mean square and momentum; Adam: second and first moment).  Sparse: Keras Adagrad on the
+    de-duplicated rows of each embedding table (ot_sparse_adagrad)."""
 
     def __init__(self, model: OneTransModel, config: OneTransConfig):
         self.model = model
         oc = config.optimizer_config
-        self.lr = float(oc.get('dense_lr', config.learning_rate))
+        self.kind, spec = dense_optimizer_spec(config)
+        self.lr = spec['lr']
         # linear warm-up of the dense learning rate over config.warmup_steps (config.py:36; the
         # reference defines warmup_steps but never applies it, so this is opt-in: apply_warmup)
         self.warmup = int(config.warmup_steps) if getattr(config, 'apply_warmup', False) else 0
         self.steps_done = 0
-        self.momentum = float(oc.get('momentum', 0.0))
-        self.rho = float(config.rmsprop_rho)
-        self.eps = float(config.rmsprop_epsilon)
+        self.eps = spec['eps']
+        if self.kind == 'rmsprop':
+            self.momentum, self.rho = spec['momentum'], spec['rho']
+        else:
+            self.beta1, self.beta2 = spec['beta1'], spec['beta2']
         self.clip = float(config.gradient_clip_norm)
         self.sparse_lr = float(oc.get('sparse_lr', 0.1))
         self.sparse_eps = float(config.adagrad_epsilon)
@@ -104,6 +110,49 @@ class OneTransOptimizer:
         if self.warmup > 0:
             return self.lr * min(1.0, self.steps_done / self.warmup)
         return self.lr
+
+    # ---------------------------------------------------------------- resumable state
+    def state_dict(self) -> Dict[str, np.ndarray]:
+        """Host copies of what a resumed run needs besides the weights: the dense kind, ``steps_done`` (Adam's bias
+        correction and the warm-up ramp), the two flat dense slots and every table's Adagrad accumulator
+        (``acc.<table>``).  Like ``OneTransModel.param_dict``, a COLLECTIVE with a row-sharded table (its
+        accumulator is all-gathered into the logical table's row order): every rank calls it."""
+        out = {'dense_kind': np.array(self.kind), 'steps_done': np.array(self.steps_done, dtype=np.int64),
+               'dense.v': self.v.detach().cpu().numpy().copy(), 'dense.m': self.m.detach().cpu().numpy().copy()}
+        for name, a in self.acc.items():
+            sh = self.model.sharded.get(name)
+            src = sh.full_table(a) if sh is not None else a
+            out[f'acc.{name}'] = src.detach().cpu().numpy().copy()
+        return out
+
+    def load_state_dict(self, d: Dict[str, np.ndarray]) -> None:
+        """Restore ``state_dict()``'s arrays.  Everything is checked before anything is written: a state of the
+        other dense kind, a missing entry or a shape that does not fit raises ValueError and leaves the optimizer
+        as it was.  A row-sharded table's accumulator keeps this rank's rows (id % world == rank)."""
+        kind = str(np.asarray(d['dense_kind']))
+        if kind != self.kind:
+            raise ValueError(f'optimizer state is for dense optimizer {kind!r}, this optimizer runs {self.kind!r}')
+        todo = []
+        for key, dst in (('dense.v', self.v), ('dense.m', self.m)):
+            todo.append((key, dst, np.asarray(d[key]) if key in d else None))
+        for name, a in self.acc.items():
+            key = f'acc.{name}'
+            arr = np.asarray(d[key]) if key in d else None
+            sh = self.model.sharded.get(name)
+            if sh is not None:
+                if arr is not None and arr.shape != (sh.num_rows, sh.E):
+                    raise ValueError(f'{key}: stored shape {arr.shape} != ({sh.num_rows}, {sh.E})')
+                todo.append((key, a[:sh.local_rows], None if arr is None else arr[sh.rank::sh.world]))
+            else:
+                todo.append((key, a, arr))
+        for key, dst, arr in todo:
+            if arr is None:
+                raise ValueError(f'optimizer state lacks {key!r}')
+            if tuple(arr.shape) != tuple(dst.shape):
+                raise ValueError(f'{key}: stored shape {tuple(arr.shape)} != {tuple(dst.shape)}')
+        for key, dst, arr in todo:
+            dst.copy_(torch.as_tensor(np.ascontiguousarray(arr), dtype=torch.float32))
+        self.steps_done = int(np.asarray(d['steps_done']))
 
     def _mark(self):
         if self.exchange_events is None:
@@ -269,8 +318,13 @@ class OneTransOptimizer:
         if ev_a is not None:
             self.exchange_events.append((ev_a, self._mark()))
         self.steps_done += 1
-        K.clip_rmsprop(m.flat.data, m.flat.grad, self.v, self.m, self.segs, self.nseg, m.layout.max_seg_elems,
-                       self.current_lr(), self.rho, self.eps, self.momentum, self.clip, device=m.flat.device)
+        if self.kind == 'rmsprop':
+            K.clip_rmsprop(m.flat.data, m.flat.grad, self.v, self.m, self.segs, self.nseg, m.layout.max_seg_elems,
+                           self.current_lr(), self.rho, self.eps, self.momentum, self.clip, device=m.flat.device)
+        else:
+            K.clip_adam(m.flat.data, m.flat.grad, self.m, self.v, self.segs, self.nseg, m.layout.max_seg_elems,
+                        self.current_lr(), self.beta1, self.beta2, self.eps, self.steps_done, self.clip,
+                        device=m.flat.device)
         m.refresh_shadow()
         for (name, keys, grads) in m._pending_sparse:
             table = m.tables[name]
@@ -394,14 +448,15 @@ class OneTransTrainer:
         return self.history
 
     def fit(self, train_batches, val_batches=None, epochs: int = 10, save_freq: int = 1,
-            early_stopping_patience: int = 5) -> Dict:
+            early_stopping_patience: int = 5, save_optimizer: bool = False) -> Dict:
         """The reference's training loop (train.py:192-279).  Per epoch: the training steps, then the validation
         steps; ``history['train_loss' / 'val_loss']`` get the epoch means (the validation loss is the training
         loss without validation data) and ``history['train_metrics' / 'val_metrics'][epoch]`` the running
         metrics' results; then ``best_model`` on a strict improvement of the validation loss, ``model_epoch_{n}``
         every ``save_freq`` epochs, the early stop after ``early_stopping_patience`` epochs without improvement,
         and the reset of both metric states.  ``final_model`` is saved after the loop.  The per-step losses and
-        the metric states stay on the device; each is read once per epoch."""
+        the metric states stay on the device; each is read once per epoch.  ``save_optimizer``: every checkpoint
+        also carries the optimizer state (``save_model(..., include_optimizer=True)``)."""
         if getattr(self, 'train_metrics', None) is None or getattr(self, 'val_metrics', None) is None:
             self.enable_metrics()
 
@@ -415,6 +470,8 @@ class OneTransTrainer:
                 m = m / otdist.world()
             return float(m)
 
+        # (a subclass's one-argument save_model keeps working while the flag is off)
+        save = (lambda name: self.save_model(name, include_optimizer=True)) if save_optimizer else self.save_model
         best_val_loss, patience_counter = float('inf'), 0
         for epoch in range(epochs):
             t0 = time.time()
@@ -433,21 +490,26 @@ class OneTransTrainer:
                   f'({time.time() - t0:.2f}s)')
             if avg_val_loss < best_val_loss:
                 best_val_loss, patience_counter = avg_val_loss, 0
-                self.save_model('best_model')
+                save('best_model')
             else:
                 patience_counter += 1
             if (epoch + 1) % save_freq == 0:
-                self.save_model(f'model_epoch_{epoch + 1}')
+                save(f'model_epoch_{epoch + 1}')
             if patience_counter >= early_stopping_patience:
                 print(f'early stop at epoch {epoch + 1}')
                 break
             self.train_metrics.reset_states()
             self.val_metrics.reset_states()
-        self.save_model('final_model')
+        save('final_model')
         return self.history
 
     # --------------------------------------------------------------- checkpoint (train.py:281-338)
-    def save_model(self, model_name: str) -> None:
+    def save_model(self, model_name: str, include_optimizer: bool = False) -> None:
+        """train.py:281-297: weights, config.json, training_history.json.  ``include_optimizer`` adds
+        ``optimizer_state.npz`` (OneTransOptimizer.state_dict: the dense slots, the step count and the tables'
+        Adagrad accumulators), so that a run resumed with ``load_model`` continues bit for bit; off by default,
+        the directory then holds the reference's three files.  Collective with a row-sharded table (every rank
+        calls it; rank 0 writes the gathered arrays)."""
         path = self.model_dir / model_name
         path.mkdir(parents=True, exist_ok=True)          # the reference never creates it (SURVEY §5)
         self.model.save_weights(str(path / 'model_weights.npz'))
@@ -457,6 +519,10 @@ class OneTransTrainer:
             # the dense optimizer's step count travels with the history, so a resumed run continues the
             # LR warm-up ramp (apply_warmup) where it stopped
             json.dump(dict(self.history, optimizer_steps=self.optimizer.steps_done), f, indent=2, default=float)
+        if include_optimizer:
+            state = self.optimizer.state_dict()
+            if not (self.model.sharded and self.model._rank() != 0):
+                np.savez(path / 'optimizer_state.npz', **state)
 
     def load_model(self, model_path: str) -> None:
         path = Path(model_path)
@@ -471,6 +537,9 @@ class OneTransTrainer:
             with open(path / 'training_history.json') as f:
                 self.history = json.load(f)
             self.optimizer.steps_done = int(self.history.pop('optimizer_steps', 0))
+        if (path / 'optimizer_state.npz').exists():      # written by save_model(..., include_optimizer=True)
+            with np.load(path / 'optimizer_state.npz', allow_pickle=False) as z:
+                self.optimizer.load_state_dict({k: z[k] for k in z.files})
 
 
 def train_one_trans_model(config_name: str = 'small', batches=None, epochs: int = 10,

@@ -1,13 +1,13 @@
 """GPU idle time per training step from rocprofv3 kernel traces (CSV).
 
-Steps are delimited by the once-per-step optimizer kernel (rmsprop_kernel) of the FIRST trace; inside each step
-the union of all kernels' [start, end) intervals (any stream, and every trace given: pass each rank's trace of a
+Steps are delimited by the once-per-step dense optimizer kernel (rmsprop_kernel, or adam_kernel in an Adam run) of
+the FIRST trace; inside each step the union of all kernels' [start, end) intervals (any stream, and every trace given: pass each rank's trace of a
 one-GPU multi-rank rehearsal, whose ranks share the device) is the busy time, the rest is idle — host launch
 latency, host syncs, or stream waits.  `boundary_ms` is the first trace's own step-boundary gap: from the end of
 its optimizer kernel to the first kernel it launches afterwards (what a host wait at the start of the next step,
 e.g. a routing split-size wait, shows up as).  Also lists the largest idle gaps of the last step.
 
-usage: python tools/timeline_gaps.py run_kernel_trace.csv [more traces ...] [--marker NAME]
+usage: python tools/timeline_gaps.py run_kernel_trace.csv [more traces ...] [--marker NAME[,NAME...]]
 """
 import csv
 import sys
@@ -20,14 +20,14 @@ def load(path):
 
 def main():
     args = sys.argv[1:]
-    marker = 'rmsprop_kernel'
+    marker = 'rmsprop_kernel,adam_kernel'
     if '--marker' in args:
         i = args.index('--marker')
         marker = args[i + 1]
         del args[i:i + 2]
     own = load(args[0])
     ks = sorted(k for p in args for k in load(p))
-    ends = [e for s, e, n in own if marker in n]
+    ends = [e for s, e, n in own if any(mk in n for mk in marker.split(','))]
     if len(ends) < 3:
         print(f'fewer than 3 {marker} launches')
         return 1
