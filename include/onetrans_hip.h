@@ -89,7 +89,9 @@ extern "C" {
 int ot_version(void);
 const char* ot_get_last_error_string(void);
 
-/* ---- mixed-parameterisation grouped GEMM (gemm.hip) --------------------------------------
+/* ---- mixed-parameterisation grouped GEMM (gemm.hip: dispatch and the register-staged kernel;
+ * gemm_plane.hip, gemm_plane_wide.hip: the plane GEMMs; gemm_images.hip: their weight images;
+ * gemm_wgrad.hip: weight gradients) ----------------------------------------------------------
  * Replaces: per-token Q/K/V Dense loop model.py:84-92 (+ weights 38-54, group rule 67-74),
  * Wo model.py:117, per-token FFN loop model.py:154-161 (weights 136-147), tokenizer Dense layers
  * model.py:211-219/254/265, task-head Dense(d/2) model.py:325-330/391, and their gradients

@@ -31,7 +31,7 @@ IMAGE_UNIT_ELEMS = 3 * TILE * 16      # one (group, column tile, 16-k stage) blo
 # past a multiple of 512 (e.g. 513) leaves a nearly empty extra round; capped, the C2 GEMM family
 # measured 332 -> 316 us/launch standalone.  Weights of >= 8 tiles (d >= 256) take ~3 rounds plus one
 # chunk per weight group (C5 +5-7%, T +2% over 768; a hard cap measured worse there).  Weights of >= 32
-# tiles (d = 512: C5's) take 4096 since the kernels place whole chunks per XCD (round 4, gemm.hip
+# tiles (d = 512: C5's) take 4096 since the kernels place whole chunks per XCD (round 4, gemm_wgrad.hip
 # wgrad_tile): shorter chunks keep a chunk's tiles closer together in the rows they stream, so more of the
 # shared rows hit the XCD's L2 (C5 1,425 / 1,438 / 1,463 / 1,466 samples/s at 1536 / 3072 / 4096 / 6144 on one
 # box; T, C3, C4 flat or -1% at 3072, so they keep 1536).  Tuning override ONETRANS_WGRAD_SLOTS (every case);

@@ -175,7 +175,7 @@ def test_pair_gelu_gemm(dev, f, N, case):
 
 def test_pair_image_without_rowmax_is_loud(dev):
     """A pair-form W2 image read by the six-product kernel (no a_rowmax) must not give plausible numbers: the image's
-    form tag multiplies NaN into the output (gemm.hip PAIR_IMAGE_TAG)."""
+    form tag multiplies NaN into the output (gemm.h PAIR_IMAGE_TAG)."""
     gen = torch.Generator().manual_seed(3)
     f, N, G, M = 512, 128, 2, 300
     rm, d = group_map(M, G, dev)

@@ -1,4 +1,4 @@
-"""Plane GEMM (pre-split B image + global_load_lds, gemm.hip plane_gemm_kernel) vs the register-
+"""Plane GEMM (pre-split B image + global_load_lds, gemm_plane.hip plane_gemm_kernel) vs the register-
 staged GEMM of the same matmul mode (split; and bf16, the one-plane form) on the same operands: every prologue / epilogue specialisation the model uses,
 ragged row maps (partial tiles, -1 rows), several weight groups, a column-tile offset into the image
 and the RMSNorm gamma folded into the image.  The register-staged kernel is itself checked against

@@ -1,4 +1,4 @@
-"""The panel form of the pair plane GEMM (gemm.hip plane_panel_kernel: one workgroup per row tile walks its column
+"""The panel form of the pair plane GEMM (gemm_plane.hip plane_panel_kernel: one workgroup per row tile walks its column
 tiles, the next tile's first stages copied during the epilogue) and the row metadata parked in LDS (ot_plane_rowmeta)
 against the one-tile kernel / the row-map reads on the same operands: every comparison is bit for bit (int32 views, so
 NaN fill patterns count).  Ragged row maps (M = 777 over 3 groups: partial tiles, -1 rows), outputs pre-filled with NaN
