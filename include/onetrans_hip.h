@@ -622,6 +622,41 @@ int ot_metrics_update(const float* probs, const float* labels, int T, int B, int
                       const double* bounds, int nb, int64_t* counts, double* sums, void* workspace,
                       size_t ws_bytes, void* stream);
 
+/* ---- grouped AUC (metrics_grouped.hip) -----------------------------------------------------
+ * The impression-weighted user-level AUC (UAUC) of the paper (complete_translation.md:178-180) over
+ * a window of n records (group id, label, score), per binary task; stream-ordered, no allocation,
+ * no host sync.  For one task, over records (g_i, y_i, s_i):
+ *   class        y_i > 0.5, as in the streaming metrics above
+ *   score order  the order of the f32 values; -0.0 ties with +0.0; every NaN ties with every other
+ *                NaN and ranks above +inf
+ *   per group u  n_pos, n_neg, and 2U = sum over (pos p, neg q) in u of (2 [s_p > s_q] + [s_p == s_q]),
+ *                an exact integer (= sum over pos of (a + b + 1 - 2 start_u) - n_pos (n_pos + 1), [a, b)
+ *                the element's tie run in the (group, score)-sorted order)
+ *   valid        n_pos > 0 and n_neg > 0; then AUC_u = (double)2U / (2.0 n_pos n_neg)
+ *   UAUC         sum_valid n_u AUC_u / sum_valid n_u, n_u = n_pos + n_neg (the caller divides: agg[0] /
+ *                agg[2], 0 with no valid group)
+ * Operands:
+ *   groups       [n] int64 ids (compared as unsigned 64-bit); group_bits (1..64) is the caller's promise
+ *                that every id is below 2^group_bits: it only shortens the sort
+ *   scores, labels  task t's n values at + t * task_stride (task_stride >= n), any float alignment
+ *   task_mask    bit t set: task t is binary and is computed; a clear bit leaves its agg row and its
+ *                group_stats zero
+ *   agg          [T][4] double, overwritten: {sum n_u AUC_u, sum AUC_u, sum n_u, number of valid groups}
+ *   num_groups   [1]: the number G of distinct ids
+ *   group_ids    [n] or NULL: the G distinct ids, ascending as unsigned 64-bit (the rest is not written)
+ *   group_stats  [T][n][3] or NULL: {n_pos, n_neg, 2U} of each distinct group in the same order, the
+ *                rows from G on zero
+ * The per-group integers are exact (64-bit integer accumulation, which commutes).  agg is reduced in a
+ * fixed order over the groups in ascending id order (thread -> wave -> workgroup -> workgroups in
+ * index order, no float atomics): bit-identical from run to run and under any permutation of the
+ * records.  1 <= T <= 32, 1 <= n < 2^31.  The workspace takes about 40 bytes per record plus the
+ * sort's scratch. */
+size_t ot_grouped_auc_workspace_size(int T, int64_t n, int group_bits);
+int ot_grouped_auc(const int64_t* groups, const float* scores, const float* labels, int T, int64_t n,
+                   int64_t task_stride, int group_bits, uint32_t task_mask, double* agg,
+                   int64_t* num_groups, int64_t* group_ids, int64_t* group_stats, void* workspace,
+                   size_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

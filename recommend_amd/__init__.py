@@ -10,7 +10,7 @@ __version__ = '1.0.0'
 from .config import OneTransConfig, get_model_config, workload_config  # noqa: F401
 from .data import create_sample_batch, criteo_batch, make_batch  # noqa: F401
 from .features import DataLoader, FeatureProcessor, OneTransDataset, SequenceProcessor  # noqa: F401
-from .metrics import StreamingMetrics, auc, keras_auc  # noqa: F401
+from .metrics import GroupedAUC, StreamingMetrics, auc, keras_auc, uauc  # noqa: F401
 
 
 def __getattr__(name):

@@ -153,6 +153,8 @@ SIGNATURES = {
                              c_size_t, P]),
     'ot_metrics_workspace_size': (c_size_t, [c_int, c_int]),
     'ot_metrics_update': (c_int, [P, P, c_int, c_int, I64, P, c_int, P, P, P, c_size_t, P]),
+    'ot_grouped_auc_workspace_size': (c_size_t, [c_int, I64, c_int]),
+    'ot_grouped_auc': (c_int, [P, P, P, c_int, I64, I64, c_int, c_uint32, P, P, P, P, P, c_size_t, P]),
 }
 
 # ABI notes (mirrors include/onetrans_hip.h): the modes/flags above; the only struct is

@@ -10,12 +10,12 @@ from __future__ import annotations
 import json
 import time
 from pathlib import Path
-from typing import Dict, Tuple
+from typing import Dict, Optional, Tuple
 
 import torch
 
 from .config import OneTransConfig
-from .metrics import StreamingMetrics
+from .metrics import GroupedAUC, StreamingMetrics
 from .model import OneTransModel
 from .trainer import _seq_inputs, _to_dev, stack_labels
 
@@ -23,11 +23,17 @@ from .trainer import _seq_inputs, _to_dev, stack_labels
 class OneTransEvaluator:
     """evaluate.py:22-129 surface: ``evaluate_offline`` over an iterable of (non_seq, seq, labels) batches."""
 
-    def __init__(self, model: OneTransModel, config: OneTransConfig, num_thresholds: int = 200):
+    def __init__(self, model: OneTransModel, config: OneTransConfig, num_thresholds: int = 200,
+                 group_feature: Optional[str] = None):
+        """``group_feature`` (for example ``'user_id'``): ``evaluate_offline`` also reports the paper's user-level
+        AUC of every binary task, ``{t}_uauc`` / ``_uauc_macro`` / ``_uauc_users`` / ``_uauc_impressions``
+        (metrics.GroupedAUC), grouped by ``non_seq[group_feature]``."""
         self.model = model
         self.config = config
         self.device = model.flat.device
         self.metrics = StreamingMetrics(config.tasks, self.device, num_thresholds)
+        self.group_feature = group_feature
+        self.grouped = GroupedAUC(config.tasks, self.device) if group_feature is not None else None
 
     @torch.no_grad()
     def evaluate_offline(self, batches) -> Dict:
@@ -41,6 +47,8 @@ class OneTransEvaluator:
         how long the launches take to issue, not how long the batch takes to compute."""
         dev = self.device
         self.metrics.reset_states()
+        if self.grouped is not None:
+            self.grouped.reset_states()
         total_samples, nbatches = 0, 0
         torch.cuda.synchronize(dev)
         t0 = time.perf_counter()
@@ -48,11 +56,19 @@ class OneTransEvaluator:
             y = labels if isinstance(labels, torch.Tensor) else stack_labels(labels, self.config.tasks, dev)
             probs = self.model.forward_probs(_to_dev(non_seq, dev), _seq_inputs(self.model, seq, dev), training=False)
             self.metrics.update(y, probs)
+            if self.grouped is not None:
+                if self.group_feature not in non_seq:
+                    raise KeyError(f'OneTransEvaluator(group_feature={self.group_feature!r}): the batch has no '
+                                   f'non-sequence feature of that name (it has {sorted(non_seq)})')
+                ids = torch.as_tensor(non_seq[self.group_feature]).reshape(-1).to(dev, torch.int64)
+                self.grouped.update(ids, y, probs)
             total_samples += int(y.shape[1])
             nbatches += 1
         torch.cuda.synchronize(dev)
         elapsed = time.perf_counter() - t0
         results = self.metrics.result(extended=True)
+        if self.grouped is not None:
+            results.update(self.grouped.result())
         results['performance'] = {
             'total_samples': total_samples,
             'avg_inference_time_per_batch': elapsed / nbatches if nbatches else 0.0,

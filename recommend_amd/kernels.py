@@ -582,6 +582,18 @@ def metrics_update(probs, labels, T, B, task_stride, bounds, nb, counts, sums, d
         _probe.end('metrics', 0.0, ev)
 
 
+def grouped_auc(groups, scores, labels, T, n, task_stride, group_bits, task_mask, agg, num_groups, group_ids=None,
+                group_stats=None, device=None) -> None:
+    """ot_grouped_auc over ``n`` records: ``agg`` [T, 4] float64 {Σ n_u·AUC_u, Σ AUC_u, Σ n_u, #valid groups},
+    ``num_groups`` [1] int64; optionally the distinct ids [n] and the per-group {n_pos, n_neg, 2U} [T, n, 3]."""
+    ws = workspace(size('ot_grouped_auc_workspace_size', T, n, group_bits), device)
+    ev = _probe.begin() if _probe is not None else None
+    call('ot_grouped_auc', ptr(groups), ptr(scores), ptr(labels), T, n, task_stride, group_bits, task_mask, ptr(agg),
+         ptr(num_groups), ptr(group_ids), ptr(group_stats), ptr(ws), ws.numel(), stream())
+    if ev is not None:
+        _probe.end('grouped_auc', 0.0, ev)
+
+
 def task_loss_logits_fwd(logits, probs, labels, T, B, loss, device=None, mse_mask: int = 0) -> None:
     """Σ_task loss (train.py:78-93) as Keras 2.12 computes it on sigmoid heads: BCE from the logits, MSE
     (bits of ``mse_mask``) from the probabilities."""

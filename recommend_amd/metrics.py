@@ -4,7 +4,12 @@
   parity estimator, identical on both sides.
 * ``keras_auc`` — ``tf.keras.metrics.AUC()`` defaults (train.py:101, evaluate.py:45): ROC over 200
   thresholds, trapezoidal interpolation.
-Both are host-side numpy over whole arrays of probabilities.
+* ``uauc`` — the paper's second offline metric, the impression-weighted user-level AUC
+  (complete_translation.md:178-180): the rank AUC inside each group (user), averaged with the groups'
+  impression counts as weights.
+All three are host-side numpy over whole arrays of probabilities.
+* ``GroupedAUC`` — ``uauc`` as a device-side metric: a device log of (group, label, probability) records,
+  appended to without a host sync, and one ``ot_grouped_auc`` call (sort + segmented rank statistic) per read.
 * ``StreamingMetrics`` — the reference's running per-step metrics (AUC, BinaryAccuracy, Precision, Recall; MSE,
   MAE; logloss and F1 for the evaluator) as device state: one HIP launch per step (``ot_metrics_update``), no
   host sync, read once per epoch.
@@ -69,6 +74,57 @@ def keras_auc(labels, probs, num_thresholds: int = 200) -> float:
     tp = len(pos_sorted) - np.searchsorted(pos_sorted, thr, side='right')
     fp = gt - tp
     return roc_trapezoid(tp, fp, y.sum(), (~y).sum())
+
+
+def _orderable(scores) -> np.ndarray:
+    """f32 scores -> uint32 keys in the same order, under the rules of ``ot_grouped_auc``: -0.0 ties with +0.0,
+    every NaN ties with every other NaN and ranks above +inf."""
+    s = np.ascontiguousarray(np.asarray(scores, dtype=np.float32).reshape(-1))
+    u = s.view(np.uint32).copy()
+    u[s == 0] = 0
+    neg = (u & np.uint32(0x80000000)) != 0
+    u = np.where(neg, ~u, u | np.uint32(0x80000000))
+    u[np.isnan(s)] = 0xFFFFFFFF
+    return u
+
+
+def uauc(groups, labels, scores) -> Dict:
+    """Impression-weighted group-level AUC of one binary task (the definition of ``ot_grouped_auc``, in float64
+    numpy): per distinct group u the class counts and the exact integer 2U = Σ_{pos p, neg q} (2·[s_p > s_q] +
+    [s_p == s_q]); a group is valid with both classes present, AUC_u = 2U / (2·n_pos·n_neg);
+    ``uauc`` = Σ_valid n_u·AUC_u / Σ_valid n_u (0 without a valid group, ``div_no_nan``).  Also ``uauc_macro`` (the
+    plain mean over valid groups), ``users`` and ``impressions`` (the valid groups and their records), and per
+    distinct group, ascending as unsigned 64-bit ids: ``groups`` [G] int64 and ``group_stats`` [G, 3] int64
+    {n_pos, n_neg, 2U}.  Scores are compared as float32: -0.0 ties with +0.0, NaNs tie with each other above +inf."""
+    g = np.ascontiguousarray(np.asarray(groups).reshape(-1).astype(np.int64)).view(np.uint64)
+    pos = np.asarray(labels).reshape(-1) > 0.5
+    key = _orderable(scores)
+    n = len(g)
+    if not (len(pos) == n and len(key) == n):
+        raise ValueError('uauc: groups, labels and scores must have the same number of records')
+    if n == 0:
+        return {'uauc': 0.0, 'uauc_macro': 0.0, 'users': 0, 'impressions': 0,
+                'groups': np.zeros(0, np.int64), 'group_stats': np.zeros((0, 3), np.int64)}
+    ids, dense = np.unique(g, return_inverse=True)
+    full = (dense.reshape(-1).astype(np.uint64) << np.uint64(32)) | key.astype(np.uint64)
+    order = np.argsort(full, kind='stable')
+    ks, ps = full[order], pos[order]
+    seg = np.concatenate([[0], np.cumsum(np.bincount(dense.reshape(-1), minlength=len(ids)))]).astype(np.int64)
+    head = np.concatenate([[True], ks[1:] != ks[:-1]])                          # tie-run heads
+    starts = np.nonzero(head)[0].astype(np.int64)
+    ends = np.concatenate([starts[1:], [n]]).astype(np.int64)
+    run = np.cumsum(head) - 1
+    twice_rank = starts[run] + ends[run] + 1 - 2 * seg[(ks >> np.uint64(32)).astype(np.int64)]
+    npos = np.add.reduceat(ps.astype(np.int64), seg[:-1])
+    nneg = np.diff(seg) - npos
+    u2 = np.add.reduceat(np.where(ps, twice_rank, 0).astype(np.int64), seg[:-1]) - npos * (npos + 1)
+    valid = (npos > 0) & (nneg > 0)
+    au = u2[valid].astype(np.float64) / (2.0 * npos[valid].astype(np.float64) * nneg[valid].astype(np.float64))
+    nu = (npos + nneg)[valid].astype(np.float64)
+    return {'uauc': float(div_no_nan(np.sum(nu * au), np.sum(nu))),
+            'uauc_macro': float(div_no_nan(np.sum(au), float(valid.sum()))),
+            'users': int(valid.sum()), 'impressions': int(nu.sum()),
+            'groups': ids.view(np.int64), 'group_stats': np.stack([npos, nneg, u2], axis=1)}
 
 
 class StreamingMetrics:
@@ -170,4 +226,171 @@ class StreamingMetrics:
             if extended:
                 res[f'{t}_f1'] = float(div_no_nan(2.0 * prec * rec, prec + rec))
                 res[f'{t}_logloss'] = float(div_no_nan(sums[i, 3], n))
+        return res
+
+
+class GroupedAUC:
+    """``uauc`` per binary task as a device-side metric.
+
+    UAUC is not additive: it needs every (group, label, probability) record of the evaluation window, grouped
+    and ranked inside each group.  The state is therefore a device log — ids [cap] int64, labels and probs
+    [T, cap] float32 — whose fill count is a host integer: ``update`` appends with slice copies (no host sync, no
+    kernel of its own) and the log doubles when full.  ``result`` is one ``ot_grouped_auc`` call over the filled
+    log and one D2H copy.  ``group_bits``: the caller's promise that every id is below 2^group_bits (for example
+    from the vocabulary size); it only shortens the sort.  On a CPU device the object holds and merges state
+    (``load_state`` / ``state`` / ``all_gather``, the empty ``result``); ``update`` and a non-empty ``result`` need
+    the GPU (no fallback)."""
+
+    def __init__(self, tasks, device, capacity: int = 1 << 20, group_bits: int = 64, binary_tasks=None):
+        import torch
+        if binary_tasks is None:
+            from .model import BINARY_TASKS as binary_tasks
+        self.tasks = list(tasks)
+        self.binary = tuple(t in binary_tasks for t in self.tasks)
+        self.device = torch.device(device)
+        if not 1 <= len(self.tasks) <= 32:
+            raise ValueError('GroupedAUC: 1..32 tasks')
+        if not 1 <= int(group_bits) <= 64 or int(capacity) < 1:
+            raise ValueError('GroupedAUC: group_bits in 1..64 and a positive capacity')
+        self.group_bits = int(group_bits)
+        self.task_mask = sum(1 << i for i, b in enumerate(self.binary) if b)
+        self.count = 0
+        self._alloc(int(capacity))
+
+    def _alloc(self, cap: int) -> None:
+        import torch
+        T = len(self.tasks)
+        self.capacity = cap
+        self._ids = torch.empty(cap, dtype=torch.int64, device=self.device)
+        self._labels = torch.empty(T, cap, dtype=torch.float32, device=self.device)
+        self._probs = torch.empty(T, cap, dtype=torch.float32, device=self.device)
+
+    def _reserve(self, total: int) -> None:
+        """Room for ``total`` records: the log doubles until they fit, the filled part moves over."""
+        if total >= 1 << 31:
+            raise ValueError('GroupedAUC: a window holds fewer than 2^31 records')
+        if total <= self.capacity:
+            return
+        cap = self.capacity
+        while cap < total:
+            cap *= 2
+        old, n = (self._ids, self._labels, self._probs), self.count
+        self._alloc(cap)
+        self._ids[:n].copy_(old[0][:n])
+        self._labels[:, :n].copy_(old[1][:, :n])
+        self._probs[:, :n].copy_(old[2][:, :n])
+
+    def _append(self, groups, labels, probs) -> None:
+        B, n = groups.shape[0], self.count
+        self._reserve(n + B)
+        self._ids[n:n + B].copy_(groups)
+        self._labels[:, n:n + B].copy_(labels)
+        self._probs[:, n:n + B].copy_(probs)
+        self.count = n + B
+
+    def update(self, groups, labels, probs) -> None:
+        """``groups``: [B] or [B, 1] int64; ``labels``, ``probs``: [T, B] float32 (any strides); device tensors.
+        No host sync."""
+        import torch
+        from . import kernels as K
+        if probs.dim() != 2 or probs.shape[0] != len(self.tasks) or labels.shape != probs.shape:
+            raise ValueError(f'GroupedAUC.update: expected two [{len(self.tasks)}, B] tensors')
+        if labels.dtype != torch.float32 or probs.dtype != torch.float32:
+            raise ValueError('GroupedAUC.update: float32 tensors expected')
+        if groups.dtype != torch.int64 or groups.numel() != probs.shape[1] or groups.dim() > 2:
+            raise ValueError('GroupedAUC.update: groups must be B int64 ids ([B] or [B, 1])')
+        if (probs.device.type != 'cuda' or labels.device != probs.device or groups.device != probs.device
+                or self.device.type != 'cuda'):
+            raise K._lib.OneTransHipError('GroupedAUC.update runs on the GPU only (there is no CPU fallback)')
+        if probs.shape[1]:
+            self._append(groups.reshape(-1), labels, probs)
+
+    def reset_states(self) -> None:
+        self.count = 0
+
+    def state(self):
+        """(groups [n], labels [T, n], probs [T, n]): views of the filled part of the log."""
+        n = self.count
+        return self._ids[:n], self._labels[:, :n], self._probs[:, :n]
+
+    def load_state(self, groups, labels, probs) -> None:
+        """Replace the log by these records."""
+        import torch
+        T = len(self.tasks)
+        g = torch.as_tensor(groups).reshape(-1).to(torch.int64)
+        y = torch.as_tensor(labels).to(torch.float32).reshape(T, -1)
+        p = torch.as_tensor(probs).to(torch.float32).reshape(T, -1)
+        if not y.shape[1] == p.shape[1] == g.shape[0]:
+            raise ValueError('GroupedAUC.load_state: groups [n], labels [T, n] and probs [T, n] expected')
+        self.count = 0
+        self._append(g, y, p)
+
+    def all_gather(self, group=None) -> None:
+        """Every rank's records, on every rank, in rank order.  In a data-parallel run one user's impressions are
+        spread over the ranks, so the state cannot be summed: the counts are all-gathered, then the logs, padded to
+        the largest count and trimmed.  Every rank then computes the same result.  A no-op outside an initialised
+        process group."""
+        import torch
+        import torch.distributed as dist
+        if not (dist.is_available() and dist.is_initialized()):
+            return
+        W, T, n = dist.get_world_size(group), len(self.tasks), self.count
+        mine = torch.tensor([n], dtype=torch.int64, device=self.device)
+        counts = [torch.empty_like(mine) for _ in range(W)]
+        dist.all_gather(counts, mine, group=group)
+        counts = [int(c) for c in torch.cat(counts).cpu()]
+        m = max(counts)
+        if m == 0:
+            return
+        # one int64 and 2T float32 rows per rank, padded to m records
+        ids = torch.zeros(m, dtype=torch.int64, device=self.device)
+        vals = torch.zeros(2 * T, m, dtype=torch.float32, device=self.device)
+        ids[:n].copy_(self._ids[:n])
+        vals[:T, :n].copy_(self._labels[:, :n])
+        vals[T:, :n].copy_(self._probs[:, :n])
+        all_ids = [torch.empty_like(ids) for _ in range(W)]
+        all_vals = [torch.empty_like(vals) for _ in range(W)]
+        dist.all_gather(all_ids, ids, group=group)
+        dist.all_gather(all_vals, vals, group=group)
+        self.count = 0
+        self._reserve(sum(counts))
+        for r, c in enumerate(counts):
+            if c:
+                self._append(all_ids[r][:c], all_vals[r][:T, :c], all_vals[r][T:, :c])
+
+    def result(self, per_group: bool = False) -> Dict:
+        """Per binary task ``{t}_uauc`` (impression-weighted), ``{t}_uauc_macro`` (the plain mean over valid groups),
+        ``{t}_uauc_users`` and ``{t}_uauc_impressions`` (the valid groups and their records); ratios are
+        ``div_no_nan``.  ``per_group`` adds ``'groups'`` (the distinct ids, ascending as unsigned 64-bit) and
+        ``{t}_group_stats`` ([G, 3] int64: n_pos, n_neg, 2U).  An empty log reports zeros without a kernel call."""
+        import torch
+        from . import kernels as K
+        T, n = len(self.tasks), self.count
+        agg, G = np.zeros((T, 4)), 0
+        ids = stats = None
+        if n > 0:
+            if self.device.type != 'cuda':
+                raise K._lib.OneTransHipError('GroupedAUC.result runs on the GPU only (there is no CPU fallback)')
+            out = torch.empty(T * 4 + 1, dtype=torch.int64, device=self.device)
+            if per_group:
+                ids = torch.empty(n, dtype=torch.int64, device=self.device)
+                stats = torch.empty(T, n, 3, dtype=torch.int64, device=self.device)
+            with torch.cuda.device(self.device):
+                K.grouped_auc(self._ids, self._probs, self._labels, T, n, self.capacity, self.group_bits,
+                              self.task_mask, out, (out, T * 4), ids, stats, device=self.device)
+            host = out.cpu().numpy()                                                 # the one D2H copy
+            agg, G = host[:T * 4].view(np.float64).reshape(T, 4), int(host[T * 4])
+        res = {}
+        if per_group:
+            res['groups'] = ids[:G].cpu().numpy() if ids is not None else np.zeros(0, np.int64)
+        for i, t in enumerate(self.tasks):
+            if not self.binary[i]:
+                continue
+            res[f'{t}_uauc'] = float(div_no_nan(agg[i, 0], agg[i, 2]))
+            res[f'{t}_uauc_macro'] = float(div_no_nan(agg[i, 1], agg[i, 3]))
+            res[f'{t}_uauc_users'] = int(agg[i, 3])
+            res[f'{t}_uauc_impressions'] = int(agg[i, 2])
+            if per_group:
+                res[f'{t}_group_stats'] = (stats[i, :G].cpu().numpy() if stats is not None
+                                           else np.zeros((0, 3), np.int64))
         return res

@@ -25,7 +25,7 @@ import torch
 from . import dist as otdist
 from . import kernels as K
 from .config import OneTransConfig, dense_optimizer_spec, get_model_config
-from .metrics import StreamingMetrics, auc, keras_auc
+from .metrics import GroupedAUC, StreamingMetrics, auc, keras_auc
 from .model import BINARY_TASKS, OneTransModel, keras_bce_loss
 
 
@@ -367,20 +367,45 @@ class OneTransTrainer:
         # the reference's running per-step metrics (train.py:95-109), off unless enable_metrics() / fit()
         self.train_metrics: Optional[StreamingMetrics] = None
         self.val_metrics: Optional[StreamingMetrics] = None
+        # the paper's user-level AUC (metrics.GroupedAUC), off unless enable_metrics(group_feature=...)
+        self.group_feature: Optional[str] = None
+        self.train_grouped: Optional[GroupedAUC] = None
+        self.val_grouped: Optional[GroupedAUC] = None
 
-    def enable_metrics(self, num_thresholds: int = 200) -> None:
+    def enable_metrics(self, num_thresholds: int = 200, group_feature: Optional[str] = None) -> None:
         """Create the running train / validation metric states (train.py:53-54, 95-109): from here on every
         ``train_step`` / ``val_step`` adds its batch to them with one stream-ordered launch (no host sync; the
-        weights do not depend on it).  Off by default: the steps then launch exactly what they always did."""
+        weights do not depend on it).  Off by default: the steps then launch exactly what they always did.
+        ``group_feature`` (for example ``'user_id'``): the steps also log ``non_seq[group_feature]`` with the batch's
+        labels and probabilities (metrics.GroupedAUC), and ``metric_results`` reports ``{t}_uauc*`` as well."""
         self.train_metrics = StreamingMetrics(self.config.tasks, self.device, num_thresholds)
         self.val_metrics = StreamingMetrics(self.config.tasks, self.device, num_thresholds)
+        self.group_feature = group_feature
+        self.train_grouped = self.val_grouped = None
+        if group_feature is not None:
+            self.train_grouped = GroupedAUC(self.config.tasks, self.device)
+            self.val_grouped = GroupedAUC(self.config.tasks, self.device)
 
     def metric_results(self, metrics: StreamingMetrics, extended: bool = False) -> Dict[str, float]:
         """``metrics.result()`` over all ranks: in a data-parallel run the state is summed over the ranks first
-        (in place, as Keras aggregates metric variables under a distribution strategy)."""
+        (in place, as Keras aggregates metric variables under a distribution strategy).  With a group feature the
+        grouped results of the same split are merged in (the records gathered from all ranks first)."""
         if otdist.world() > 1:
             metrics.all_reduce()
-        return metrics.result(extended)
+        res = metrics.result(extended)
+        grouped = (getattr(self, 'train_grouped', None) if metrics is self.train_metrics else
+                   getattr(self, 'val_grouped', None) if metrics is self.val_metrics else None)
+        if grouped is not None:
+            if otdist.world() > 1:
+                grouped.all_gather()
+            res.update(grouped.result())
+        return res
+
+    def _group_ids(self, non_seq) -> torch.Tensor:
+        if self.group_feature not in non_seq:
+            raise KeyError(f'enable_metrics(group_feature={self.group_feature!r}): the batch has no non-sequence '
+                           f'feature of that name (it has {sorted(non_seq)})')
+        return torch.as_tensor(non_seq[self.group_feature]).reshape(-1).to(self.device, torch.int64)
 
     # --------------------------------------------------------------- steps
     def train_step(self, batch_data, next_batch=None) -> Dict[str, torch.Tensor]:
@@ -401,6 +426,8 @@ class OneTransTrainer:
         self.optimizer.step()
         if self.train_metrics is not None:               # train.py:140-150
             self.train_metrics.update(y, probs.detach())
+        if getattr(self, 'train_grouped', None) is not None:
+            self.train_grouped.update(self._group_ids(non_seq), y, probs.detach())
         return {'total_loss': loss.detach(), 'probs': probs.detach()}
 
     @torch.no_grad()
@@ -413,6 +440,8 @@ class OneTransTrainer:
         loss = keras_bce_loss(y, probs, self.config.tasks, label_rank(labels))
         if self.val_metrics is not None:                 # train.py:176-185
             self.val_metrics.update(y, probs)
+        if getattr(self, 'val_grouped', None) is not None:
+            self.val_grouped.update(self._group_ids(non_seq), y, probs)
         return {'total_loss': loss, 'probs': probs}
 
     def evaluate(self, batches) -> Dict[str, float]:
@@ -498,10 +527,51 @@ class OneTransTrainer:
             if patience_counter >= early_stopping_patience:
                 print(f'early stop at epoch {epoch + 1}')
                 break
-            self.train_metrics.reset_states()
-            self.val_metrics.reset_states()
+            self.reset_metrics()
         save('final_model')
         return self.history
+
+    def reset_metrics(self) -> None:
+        """Reset every running metric state, the grouped ones included."""
+        for m in (self.train_metrics, self.val_metrics, getattr(self, 'train_grouped', None),
+                  getattr(self, 'val_grouped', None)):
+            if m is not None:
+                m.reset_states()
+
+    def progressive_validation(self, batches, period_of=None) -> Dict:
+        """The paper's next-batch evaluation ("record the predictions of each mini-batch in evaluation mode, then
+        train on that batch"): for every batch ``val_step`` on it, then ``train_step`` on it.  ``period_of(i,
+        batch)`` names the batch's period (the paper: the day); at each change of period the validation metrics are
+        read (``metric_results``), stored under the period that ended, and reset.  Without ``period_of`` there is
+        one period.  The validation states are reset before the first batch, so what they held is not counted.
+        Returns ``{'periods': {name: metrics}, 'macro': {metric: mean over the periods}}``."""
+        if getattr(self, 'val_metrics', None) is None:
+            self.enable_metrics()
+        periods: Dict = {}
+
+        def reset() -> None:
+            for m in (self.val_metrics, getattr(self, 'val_grouped', None)):
+                if m is not None:
+                    m.reset_states()
+
+        def close(name) -> None:
+            periods[name] = self.metric_results(self.val_metrics)
+            reset()
+
+        reset()
+        current, seen = None, False
+        for i, b in enumerate(batches):
+            name = period_of(i, b) if period_of is not None else 0
+            if seen and name != current:
+                close(current)
+            current, seen = name, True
+            self.val_step(b)
+            self.train_step(b)
+        if seen:
+            close(current)
+        keys = sorted({k for m in periods.values() for k in m})
+        macro = {k: float(np.mean([m[k] for m in periods.values() if k in m])) for k in keys}
+        return {'periods': periods, 'macro': macro}
 
     # --------------------------------------------------------------- checkpoint (train.py:281-338)
     def save_model(self, model_name: str, include_optimizer: bool = False) -> None:
