@@ -657,6 +657,40 @@ int ot_grouped_auc(const int64_t* groups, const float* scores, const float* labe
                    int64_t* num_groups, int64_t* group_ids, int64_t* group_stats, void* workspace,
                    size_t ws_bytes, void* stream);
 
+/* ---- ranking (rank.hip) --------------------------------------------------------------------
+ * Per-request top-K of scored candidates, the serving step after stage II: C candidates with T task
+ * probabilities each and a request index, R requests, K slots per request; stream-ordered, no
+ * allocation, no host sync, no device-to-host copy.
+ *   probs        f32, task t's C values at + t * task_stride (task_stride >= C): the head's [T, C]
+ *   weights_host T host floats, read at call time and passed to the kernel by value
+ *   fused score  f[c], f32, in task order t = 0..T-1 with one rounding per step:
+ *                  OT_RANK_SUM      f = fmaf(w_t, p_t, f) from 0.0f (T = 1, w = 1: the bits of p)
+ *                  OT_RANK_PRODUCT  f = f * p_t over the tasks with w_t != 0, from 1.0f
+ *   order        orderable(f) = 0 for a NaN; else with u = bits(f + 0.0f) (-0 ties with +0),
+ *                (u & 0x80000000) ? ~u : (u | 0x80000000).  A NaN ranks below -inf.  The 64-bit key is
+ *                orderable(f) << 32 | (0xFFFFFFFF - c): keys are distinct, a higher score wins and equal
+ *                scores go to the lower candidate index.
+ *   membership   candidate c belongs to request req[c] when 0 <= req[c] < R.  Any other value excludes
+ *                it (the way to mask filtered candidates): it is never used as an index and appears in
+ *                no row.
+ *   outputs      for request r with n_r members and k_r = min(K, n_r):
+ *                  top_idx   [R][K] int32: [r][0..k_r) the candidates of the k_r largest keys, in
+ *                            descending key order; the slots from k_r on are -1
+ *                  top_score [R][K] f32: f[top_idx], bit for bit (a NaN included); the slots from k_r on
+ *                            are -inf
+ *                  count     [R] int32: k_r
+ *                  fused_out [C] f32 or NULL: f of every candidate, excluded ones included
+ * The answer is unique, so the outputs are bit-identical from run to run and under any arrival order
+ * of the integer atomics inside.  1 <= K <= 1024, 1 <= T <= 32, 0 <= C <= INT32_MAX, R >= 0; R = 0 or
+ * C = 0 writes the empty answer (every slot padding, every count 0).  The workspace takes 16 bytes per
+ * candidate and 8 per request. */
+#define OT_RANK_SUM 0
+#define OT_RANK_PRODUCT 1
+size_t ot_rank_topk_workspace_size(int R, int64_t C, int K);
+int ot_rank_topk(const float* probs, int64_t task_stride, int T, const float* weights_host, int mode,
+                 const int32_t* req, int64_t C, int R, int K, int32_t* top_idx, float* top_score,
+                 int32_t* count, float* fused_out, void* workspace, size_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

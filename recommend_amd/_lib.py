@@ -28,6 +28,9 @@ OT_ATTN_DQ_PART_BF16 = 4
 OT_WG_D_BF16 = 8
 OT_MATMUL_F32, OT_MATMUL_SPLIT_BF16, OT_MATMUL_BF16 = 0, 1, 2
 OT_FP8_DEQUANT, OT_FP8_TWO_TERM = 1, 2
+OT_RANK_SUM, OT_RANK_PRODUCT = 0, 1
+RANK_MODES = {'sum': OT_RANK_SUM, 'product': OT_RANK_PRODUCT}
+RANK_MAX_K = 1024
 MATMUL_MODES = {'f32': OT_MATMUL_F32, 'split': OT_MATMUL_SPLIT_BF16, 'bf16': OT_MATMUL_BF16}
 
 
@@ -155,6 +158,8 @@ SIGNATURES = {
     'ot_metrics_update': (c_int, [P, P, c_int, c_int, I64, P, c_int, P, P, P, c_size_t, P]),
     'ot_grouped_auc_workspace_size': (c_size_t, [c_int, I64, c_int]),
     'ot_grouped_auc': (c_int, [P, P, P, c_int, I64, I64, c_int, c_uint32, P, P, P, P, P, c_size_t, P]),
+    'ot_rank_topk_workspace_size': (c_size_t, [c_int, I64, c_int]),
+    'ot_rank_topk': (c_int, [P, I64, c_int, P, c_int, P, I64, c_int, c_int, P, P, P, P, P, c_size_t, P]),
 }
 
 # ABI notes (mirrors include/onetrans_hip.h): the modes/flags above; the only struct is

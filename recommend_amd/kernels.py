@@ -594,6 +594,26 @@ def grouped_auc(groups, scores, labels, T, n, task_stride, group_bits, task_mask
         _probe.end('grouped_auc', 0.0, ev)
 
 
+def rank_topk(probs, task_stride, T, weights, mode, req, C, R, K, top_idx, top_score, count, fused_out=None,
+              device=None) -> None:
+    """ot_rank_topk: per request the ``K`` best of its candidates under the fused score (``mode`` 'sum':
+    Σ w_t p_t by fma in task order; 'product': Π p_t over w_t != 0), ties to the lower candidate index.
+    ``probs`` task-major with ``task_stride``, ``weights`` T host floats (passed by value, no device copy),
+    ``req`` [C] int32 (outside [0, R): excluded).  Writes ``top_idx`` [R, K] int32 (-1 padded), ``top_score``
+    [R, K] f32 (-inf padded), ``count`` [R] int32 and optionally ``fused_out`` [C]."""
+    if mode not in _lib.RANK_MODES:
+        raise ValueError(f'rank mode {mode!r}: expected one of {sorted(_lib.RANK_MODES)}')
+    if len(weights) != T:
+        raise ValueError(f'rank_topk: {len(weights)} weights for {T} tasks')
+    wts = (ctypes.c_float * max(T, 1))(*[float(w) for w in weights])
+    ws = workspace(size('ot_rank_topk_workspace_size', R, C, K), device)
+    ev = _probe.begin() if _probe is not None else None
+    call('ot_rank_topk', ptr(probs), task_stride, T, wts, _lib.RANK_MODES[mode], ptr(req), C, R, K, ptr(top_idx),
+         ptr(top_score), ptr(count), ptr(fused_out), ptr(ws), ws.numel(), stream())
+    if ev is not None:
+        _probe.end('rank', 0.0, ev)
+
+
 def task_loss_logits_fwd(logits, probs, labels, T, B, loss, device=None, mse_mask: int = 0) -> None:
     """Σ_task loss (train.py:78-93) as Keras 2.12 computes it on sigmoid heads: BCE from the logits, MSE
     (bits of ``mse_mask``) from the probabilities."""

@@ -213,11 +213,9 @@ class OneTransServer:
         return RequestCache(R, cache.L_S + dL, layers, cache.present)
 
     # ------------------------------------------------------------------ stage II
-    @torch.no_grad()
-    @K.in_model_precision
-    def score(self, cache: RequestCache, req: torch.Tensor, non_seq_features: Dict[str, torch.Tensor]):
-        """Candidates' NS tokens (model.py:239-254) through every layer against their request's cache;
-        returns {task: probs [C, 1]} like ``OneTransModel.forward`` (model.py:384-391)."""
+    def _stage2(self, who: str, cache: RequestCache, req: torch.Tensor, non_seq_features: Dict[str, torch.Tensor]):
+        """Candidates' NS tokens (model.py:239-254) through every layer against their request's cache and the
+        heads: (probs [T, C], req as device int32 [C])."""
         from .model import _Head, _Tokenize
         m = self.m
         cfg = m.config
@@ -228,19 +226,19 @@ class OneTransServer:
         C = plan['B']
         req = torch.as_tensor(req)
         if req.numel() != C:
-            raise ValueError(f'score: {req.numel()} request indices for {C} candidates')
+            raise ValueError(f'{who}: {req.numel()} request indices for {C} candidates')
         # the cached-attention kernel indexes the K/V cache with req unchecked: validate before launch
         # (host indices directly; device indices with one min/max read-back)
         lo, hi = (int(v) for v in torch.aminmax(req.reshape(-1).to(torch.int64)))
         if lo < 0 or hi >= cache.R:
-            raise ValueError(f'score: request index out of range [0, {cache.R}) (min {lo}, max {hi})')
+            raise ValueError(f'{who}: request index out of range [0, {cache.R}) (min {lo}, max {hi})')
         req = req.to(dev, torch.int32).contiguous()
         x = _Tokenize.apply(m.flat, m, plan)                              # [C*L_NS, d]: NS tokens only
         for l, e in enumerate(self.schedule(cache.L_S)):
             s, n, kN = e['s'], e['n'], e['kN']
             lay = cache.layers[l]
             if lay['Ic'] != s:
-                raise OneTransHipError('score: request cache does not match the schedule')
+                raise OneTransHipError(f'{who}: request cache does not match the schedule')
 
             def attn(qkv, lay=lay, s=s, n=n, kN=kN):
                 o = torch.empty(C * kN, d, device=dev)
@@ -250,7 +248,54 @@ class OneTransServer:
 
             x, _ = self._block(l, x, C, n, kN, s, e['I'], attn)
         probs, _ = _Head.apply(m.flat, x, m)                               # [T, C]
-        return {t: probs[i].view(-1, 1) for i, t in enumerate(cfg.tasks)}
+        return probs, req
+
+    @torch.no_grad()
+    @K.in_model_precision
+    def score(self, cache: RequestCache, req: torch.Tensor, non_seq_features: Dict[str, torch.Tensor]):
+        """Stage II for C candidates: returns {task: probs [C, 1]} like ``OneTransModel.forward``
+        (model.py:384-391)."""
+        probs, _ = self._stage2('score', cache, req, non_seq_features)
+        return {t: probs[i].view(-1, 1) for i, t in enumerate(self.m.config.tasks)}
+
+    def _rank_weights(self, weights: Optional[Dict[str, float]]) -> List[float]:
+        tasks = list(self.m.config.tasks)
+        if weights is None:
+            return [1.0] * len(tasks)
+        unknown = [t for t in weights if t not in tasks]
+        if unknown:
+            raise ValueError(f'rank: unknown task(s) {unknown} in weights (the model has {tasks})')
+        return [float(weights.get(t, 1.0)) for t in tasks]
+
+    @torch.no_grad()
+    @K.in_model_precision
+    def rank(self, cache: RequestCache, req: torch.Tensor, non_seq_features: Dict[str, torch.Tensor], k: int,
+             weights: Optional[Dict[str, float]] = None, mode: str = 'sum', return_probs: bool = False):
+        """Stage II as in ``score``, then per request the ``k`` best of its candidates under one fused score
+        (ot_rank_topk on the heads' [T, C] output): ``mode`` 'sum' ranks by Σ_task w·p, 'product' by Π_task p over
+        the tasks whose weight is not 0 (pCTR · pCVR).  ``weights`` {task: float}, default 1 for every task.
+        Equal scores go to the lower candidate index.  Returns device tensors, no host sync:
+        'index' int32 [R, k] (positions in this call's candidate batch, -1 past 'count'), 'score' f32 [R, k]
+        (-inf past 'count'), 'count' int32 [R] = min(k, the request's candidates); with ``return_probs`` also
+        'probs' {task: [C, 1]} as ``score`` returns."""
+        from ._lib import RANK_MAX_K, RANK_MODES
+        k = int(k)
+        if k < 1 or k > RANK_MAX_K:
+            raise ValueError(f'rank: k={k} out of range (1..{RANK_MAX_K})')
+        if mode not in RANK_MODES:
+            raise ValueError(f'rank: mode {mode!r}, expected one of {sorted(RANK_MODES)}')
+        w = self._rank_weights(weights)
+        probs, req = self._stage2('rank', cache, req, non_seq_features)
+        T, C = probs.shape
+        R, dev = cache.R, probs.device
+        out = {'index': torch.empty(R, k, dtype=torch.int32, device=dev),
+               'score': torch.empty(R, k, dtype=torch.float32, device=dev),
+               'count': torch.empty(R, dtype=torch.int32, device=dev)}
+        K.rank_topk(probs, probs.stride(0), T, w, mode, req, C, R, k, out['index'], out['score'], out['count'],
+                    device=dev)
+        if return_probs:
+            out['probs'] = {t: probs[i].view(-1, 1) for i, t in enumerate(self.m.config.tasks)}
+        return out
 
     @torch.no_grad()
     @K.in_model_precision
@@ -340,10 +385,8 @@ class OneTransInferenceEngine:
             self._update_stats(False, 0.0, len(batch_data))
             raise
 
-    def score_candidates(self, user_features: Dict, sequence_features: Dict, candidates: List[Dict]):
-        """One request (user + sequences), many candidates (item / context features each): stage I once,
-        stage II for all candidates (paper §3.5.1).  Same results as ``batch_inference`` on the
-        (user, candidate, sequences) samples."""
+    def _one_request(self, user_features: Dict, sequence_features: Dict, candidates: List[Dict]):
+        """Stage I for one request and its candidates' NS features on the device: (cache, features)."""
         import numpy as np
         dev = self.model.device
         _, seq = self.preprocess_input({}, {}, {}, sequence_features)
@@ -353,9 +396,43 @@ class OneTransInferenceEngine:
             ns[k] = np.repeat(np.asarray(v).reshape(-1)[:1], len(candidates))
         for k in candidates[0]:
             ns[k] = np.concatenate([np.asarray(c[k]).reshape(-1) for c in candidates])
-        nsd = {k: torch.as_tensor(v).reshape(-1, 1).to(dev) for k, v in ns.items()}
+        return cache, {k: torch.as_tensor(v).reshape(-1, 1).to(dev) for k, v in ns.items()}
+
+    def score_candidates(self, user_features: Dict, sequence_features: Dict, candidates: List[Dict]):
+        """One request (user + sequences), many candidates (item / context features each): stage I once,
+        stage II for all candidates (paper §3.5.1).  Same results as ``batch_inference`` on the
+        (user, candidate, sequences) samples."""
+        cache, nsd = self._one_request(user_features, sequence_features, candidates)
         out = self.server.score(cache, torch.zeros(len(candidates), dtype=torch.int32), nsd)
         return [{t: float(p[i, 0]) for t, p in out.items()} for i in range(len(candidates))]
+
+    def rank_candidates(self, user_features: Dict, sequence_features: Dict, candidates: List[Dict], k: int,
+                        weights: Optional[Dict[str, float]] = None, mode: str = 'sum'):
+        """``score_candidates``' path, then the ``k`` best candidates under the fused score (``OneTransServer.rank``):
+        a list of (candidate index, fused score, {task: prob}) in rank order, min(k, len(candidates)) long.  Only
+        the winners come back: their indices, scores and per-task probabilities are gathered on the device and
+        copied to the host in one transfer."""
+        import time
+        t0 = time.time()
+        try:
+            cache, nsd = self._one_request(user_features, sequence_features, candidates)
+            C = len(candidates)
+            out = self.server.rank(cache, torch.zeros(C, dtype=torch.int32), nsd, k, weights=weights, mode=mode,
+                                   return_probs=True)
+            n = min(int(k), C)                                             # one request holding every candidate
+            idx = out['index'][0, :n]
+            tasks = list(self.config.tasks)
+            won = torch.stack([out['probs'][t][:, 0] for t in tasks])[:, idx.long()]          # [T, n]
+            packed = torch.cat([idx.view(1, n), out['score'][0, :n].view(torch.int32).view(1, n),
+                                won.view(torch.int32)]).cpu().numpy()                          # the one copy
+            score, probs = packed[1].view('float32'), packed[2:].view('float32')
+            res = [(int(packed[0, j]), float(score[j]), {t: float(probs[i, j]) for i, t in enumerate(tasks)})
+                   for j in range(n)]
+            self._update_stats(True, (time.time() - t0) * 1e3)
+            return res
+        except Exception:
+            self._update_stats(False, 0.0)
+            raise
 
     # ------------------------------------------------------------------ inference_example.py:181-219
     def _update_stats(self, success: bool, latency: float, batch_size: int = 1):
