@@ -172,12 +172,15 @@ int fail(int code, const char* fmt, ...);
     if (!(cond)) return ::ot::fail(OT_ERR_INVALID_ARG, __VA_ARGS__); \
   } while (0)
 
-#define OT_LAUNCH_CHECK(name)                                                        \
-  do {                                                                              \
-    hipError_t _e = hipGetLastError();                                              \
-    if (_e != hipSuccess)                                                           \
-      return ::ot::fail(OT_ERR_HIP, "%s: %s", name, hipGetErrorString(_e));         \
-  } while (0)
+// a HIP (or rocPRIM) error as an OT_* status, described under the caller's label
+inline int hip_status(hipError_t e, const char* label) {
+  return e == hipSuccess ? OT_OK : fail(OT_ERR_HIP, "%s: %s", label, hipGetErrorString(e));
+}
+
+// an OT_* status that is not OT_OK leaves the calling function (the callee has set the error string)
+#define OT_TRY(expr) do { const int _rc = (expr); if (_rc != OT_OK) return _rc; } while (0)
+
+#define OT_LAUNCH_CHECK(name) OT_TRY(::ot::hip_status(hipGetLastError(), name))
 
 // ---- dropout: counter-based mask (oracle/keras_math.py::dropout_keep) ---------------
 __device__ __forceinline__ uint32_t fmix32(uint32_t h) {
@@ -280,6 +283,20 @@ __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
   return v;
+}
+__device__ __forceinline__ double wave_sum(double v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
+// sum over a 256-thread block (every thread calls it, once per kernel: one barrier and one LDS buffer): the four
+// wave sums added as (w0 + w1) + (w2 + w3).  The callers use the result in thread 0.
+__device__ __forceinline__ float block_sum_256(float v) {
+  __shared__ float red[4];
+  v = wave_sum(v);
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+  __syncthreads();
+  return (red[0] + red[1]) + (red[2] + red[3]);
 }
 __device__ __forceinline__ float wave_max(float v) {
 #pragma unroll

@@ -9,11 +9,7 @@
 //   4. clip_by_norm(clip) over the unique-row gradient (one device scalar, no host sync)
 //   5. acc[r] += g^2 ; w[r] -= lr * g / sqrt(acc[r] + eps)
 // HBM-bound: the row reads in step 3 and the table/accumulator row RMW in step 5.
-#include <cstring>
-#include <rocprim/device/device_radix_sort.hpp>
-#include <rocprim/device/device_scan.hpp>
-
-#include "common.h"
+#include "keyed.h"
 
 namespace ot {
 
@@ -24,12 +20,6 @@ __global__ void keys_prep_kernel(const int64_t* __restrict__ keys, int64_t n, in
   int64_t k = keys[i];
   k32[i] = (k >= 0 && k < num_rows) ? (uint32_t)k : 0xFFFFFFFFu;   // invalid keys sort last, skipped
   vals[i] = (int32_t)i;
-}
-
-__global__ void head_flags_kernel(const uint32_t* __restrict__ k, int64_t n, int32_t* flags) {
-  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  flags[i] = (i == 0 || k[i] != k[i - 1]) ? 1 : 0;
 }
 
 __global__ void seg_start_kernel(const int32_t* __restrict__ flags, const int32_t* __restrict__ pos, int64_t n,
@@ -66,11 +56,7 @@ __global__ __launch_bounds__(256) void piece_sum_kernel(const float* __restrict_
   const int lt = threadIdx.x % tps;
   const int U = nuniq[0];
   if (pc >= pstart[U]) return;
-  int lo = 0, hi = U - 1;                         // largest s with pstart[s] <= pc
-  while (lo < hi) {
-    const int mid = (lo + hi + 1) >> 1;
-    if (pstart[mid] <= pc) lo = mid; else hi = mid - 1;
-  }
+  const int lo = last_start_le(pstart, U, pc);   // the piece's segment
   const int i0 = seg_start[lo] + (int)(pc - pstart[lo]) * PIECE;
   const int i1 = min(i0 + PIECE, seg_start[lo + 1]);
   for (int c = lt * 4; c < E; c += tps * 4) {
@@ -86,7 +72,6 @@ __global__ __launch_bounds__(256) void seg_sum_kernel(const float* __restrict__ 
                                                       const int32_t* __restrict__ pstart,
                                                       const int32_t* __restrict__ nuniq, int tps, float* gsum,
                                                       float* sq_part) {
-  __shared__ float red[4];
   const int spb = 256 / tps;
   const int64_t s = (int64_t)blockIdx.x * spb + threadIdx.x / tps;
   const int lt = threadIdx.x % tps;
@@ -100,22 +85,17 @@ __global__ __launch_bounds__(256) void seg_sum_kernel(const float* __restrict__ 
       sq += acc.x * acc.x + acc.y * acc.y + acc.z * acc.z + acc.w * acc.w;
     }
   }
-  sq = wave_sum(sq);
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = sq;
-  __syncthreads();
-  if (threadIdx.x == 0) sq_part[blockIdx.x] = (red[0] + red[1]) + (red[2] + red[3]);
+  sq = block_sum_256(sq);
+  if (threadIdx.x == 0) sq_part[blockIdx.x] = sq;
 }
 
 __global__ __launch_bounds__(256) void clip_scale_kernel(const float* __restrict__ part, int n, float clip,
                                                          float* scale) {
-  __shared__ float red[4];
   float s = 0.f;
   for (int i = threadIdx.x; i < n; i += 256) s += part[i];
-  s = wave_sum(s);
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
-  __syncthreads();
+  s = block_sum_256(s);
   if (threadIdx.x == 0) {
-    const float l2 = sqrtf((red[0] + red[1]) + (red[2] + red[3]));
+    const float l2 = sqrtf(s);
     scale[0] = clip > 0.f ? clip / fmaxf(l2, clip) : 1.f;
   }
 }
@@ -167,16 +147,13 @@ __global__ __launch_bounds__(256) void scatter_rows_kernel(float* dense, int E, 
 
 // sum of squares of a dense gradient: per-block partials (fixed grid-stride order: deterministic)
 __global__ __launch_bounds__(256) void dense_sumsq_kernel(const float* __restrict__ g, int64_t n4, float* part) {
-  __shared__ float red[4];
   float sq = 0.f;
   for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += (int64_t)gridDim.x * 256) {
     const f32x4 v = *reinterpret_cast<const f32x4*>(g + 4 * i);
     sq += v.x * v.x + v.y * v.y + v.z * v.z + v.w * v.w;
   }
-  sq = wave_sum(sq);
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = sq;
-  __syncthreads();
-  if (threadIdx.x == 0) part[blockIdx.x] = (red[0] + red[1]) + (red[2] + red[3]);
+  sq = block_sum_256(sq);
+  if (threadIdx.x == 0) part[blockIdx.x] = sq;
 }
 
 // Keras Adagrad over every row; rows with a zero gradient are left bitwise unchanged (acc + 0,
@@ -202,13 +179,10 @@ constexpr int DENSE_GRID = 2048;
 
 // fixed-order sum of the per-block squared-norm partials (one block)
 __global__ __launch_bounds__(256) void sum_parts_kernel(const float* __restrict__ part, int n, float* out) {
-  __shared__ float red[4];
   float s = 0.f;
   for (int i = threadIdx.x; i < n; i += 256) s += part[i];
-  s = wave_sum(s);
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
-  __syncthreads();
-  if (threadIdx.x == 0) out[0] = (red[0] + red[1]) + (red[2] + red[3]);
+  s = block_sum_256(s);
+  if (threadIdx.x == 0) out[0] = s;
 }
 
 // clip scale from an externally reduced squared norm (row-sharded tables: sum over owners)
@@ -224,11 +198,8 @@ struct SparseWs {
   int32_t *v_in, *v_out, *flags, *pos, *seg_start, *nuniq, *pcount, *pstart;
   float *gsum, *psum, *sq_part, *scale;
   void* tmp;
-  size_t tmp_bytes;
-  size_t total;
+  size_t tmp_bytes, total;
 };
-
-inline size_t al(size_t x) { return (x + 255) & ~(size_t)255; }
 
 inline int tps_for(int E) {
   int t = E / 4;
@@ -237,30 +208,20 @@ inline int tps_for(int E) {
 
 SparseWs carve(void* base, int64_t n, int E) {
   SparseWs w{};
-  size_t sort_bytes = 0, scan_bytes = 0;
-  (void)rocprim::radix_sort_pairs(nullptr, sort_bytes, (uint32_t*)nullptr, (uint32_t*)nullptr, (int32_t*)nullptr,
-                                  (int32_t*)nullptr, (size_t)n, 0, 32);
-  (void)rocprim::inclusive_scan(nullptr, scan_bytes, (int32_t*)nullptr, (int32_t*)nullptr, (size_t)n,
-                                rocprim::plus<int32_t>());
-  size_t escan_bytes = 0;
-  (void)rocprim::exclusive_scan(nullptr, escan_bytes, (int32_t*)nullptr, (int32_t*)nullptr, 0, (size_t)n + 1,
-                                rocprim::plus<int32_t>());
-  w.tmp_bytes = sort_bytes > scan_bytes ? sort_bytes : scan_bytes;
-  w.tmp_bytes = w.tmp_bytes > escan_bytes ? w.tmp_bytes : escan_bytes;
+  w.tmp_bytes = std::max({sort_pairs_bytes<uint32_t>(n, 32), inclusive_scan_bytes<int32_t>(n),
+                          exclusive_scan_bytes<int32_t>(n + 1)});
   const int spb = 256 / tps_for(E);
   const int64_t nblk = (n + spb - 1) / spb;
-  char* p = (char*)base;
-  size_t off = 0;
-  auto take = [&](size_t bytes) { char* r = p ? p + off : nullptr; off += al(bytes); return (void*)r; };
-  w.k_in = (uint32_t*)take(n * 4); w.k_out = (uint32_t*)take(n * 4);
-  w.v_in = (int32_t*)take(n * 4); w.v_out = (int32_t*)take(n * 4);
-  w.flags = (int32_t*)take(n * 4); w.pos = (int32_t*)take(n * 4);
-  w.seg_start = (int32_t*)take((n + 1) * 4); w.nuniq = (int32_t*)take(4);
-  w.pcount = (int32_t*)take((n + 1) * 4); w.pstart = (int32_t*)take((n + 1) * 4);
-  w.gsum = (float*)take((size_t)n * E * 4); w.psum = (float*)take((size_t)(n + n / PIECE + 1) * E * 4);
-  w.sq_part = (float*)take(nblk * 4); w.scale = (float*)take(4);
-  w.tmp = take(w.tmp_bytes);
-  w.total = off;
+  Carver c(base);
+  w.k_in = c.take<uint32_t>(n); w.k_out = c.take<uint32_t>(n);
+  w.v_in = c.take<int32_t>(n); w.v_out = c.take<int32_t>(n);
+  w.flags = c.take<int32_t>(n); w.pos = c.take<int32_t>(n);
+  w.seg_start = c.take<int32_t>(n + 1); w.nuniq = c.take<int32_t>(1);
+  w.pcount = c.take<int32_t>(n + 1); w.pstart = c.take<int32_t>(n + 1);
+  w.gsum = c.take<float>((size_t)n * E); w.psum = c.take<float>((size_t)(n + n / PIECE + 1) * E);
+  w.sq_part = c.take<float>(nblk); w.scale = c.take<float>(1);
+  w.tmp = c.take<char>(w.tmp_bytes);
+  w.total = c.total();
   return w;
 }
 
@@ -275,7 +236,7 @@ extern "C" size_t ot_sparse_adagrad_workspace_size(int64_t n, int E) {
 
 // steps 1-3 (+ the per-block squared-norm partials of the unique-row sums): fills w.k_out,
 // w.seg_start, w.nuniq, w.gsum, w.sq_part
-static int segment_rows(const SparseWs& w, int E, int64_t num_rows, const int64_t* keys, const float* grads,
+static int segment_rows(SparseWs& w, int E, int64_t num_rows, const int64_t* keys, const float* grads,
                         int64_t n, hipStream_t s) {
   const unsigned g1 = ceil_div(n, 256);
   hipLaunchKernelGGL(keys_prep_kernel, dim3(g1), dim3(256), 0, s, keys, n, num_rows, w.k_in, w.v_in);
@@ -283,23 +244,16 @@ static int segment_rows(const SparseWs& w, int E, int64_t num_rows, const int64_
   int end_bit = 1;
   while (end_bit < 32 && ((uint64_t)1 << end_bit) < (uint64_t)num_rows + 1) ++end_bit;
   // 2^end_bit > num_rows: the invalid sentinel's low bits (2^end_bit - 1) still sort after every valid key
-  size_t tb = w.tmp_bytes;
-  hipError_t e = rocprim::radix_sort_pairs(w.tmp, tb, w.k_in, w.k_out, w.v_in, w.v_out, (size_t)n, 0, end_bit, s);
-  if (e != hipSuccess) return fail(OT_ERR_HIP, "ot_sparse_adagrad(sort): %s", hipGetErrorString(e));
-  hipLaunchKernelGGL(head_flags_kernel, dim3(g1), dim3(256), 0, s, w.k_out, n, w.flags);
-  OT_LAUNCH_CHECK("ot_sparse_adagrad(flags)");
-  tb = w.tmp_bytes;
-  e = rocprim::inclusive_scan(w.tmp, tb, w.flags, w.pos, (size_t)n, rocprim::plus<int32_t>(), s);
-  if (e != hipSuccess) return fail(OT_ERR_HIP, "ot_sparse_adagrad(scan): %s", hipGetErrorString(e));
+  OT_TRY(sort_pairs(w.tmp, w.tmp_bytes, w.k_in, w.k_out, w.v_in, w.v_out, n, end_bit, s, "ot_sparse_adagrad(sort)"));
+  OT_TRY(run_index(w.k_out, n, w.flags, w.pos, w.tmp, w.tmp_bytes, s, "ot_sparse_adagrad(flags)",
+                   "ot_sparse_adagrad(scan)"));
   hipLaunchKernelGGL(seg_start_kernel, dim3(g1), dim3(256), 0, s, w.flags, w.pos, n, w.seg_start, w.nuniq);
   OT_LAUNCH_CHECK("ot_sparse_adagrad(segments)");
   const int tps = tps_for(E);
   hipLaunchKernelGGL(piece_count_kernel, dim3(ceil_div(n + 1, 256)), dim3(256), 0, s, w.seg_start, w.nuniq, n,
                      w.pcount);
   OT_LAUNCH_CHECK("ot_sparse_adagrad(pieces)");
-  tb = w.tmp_bytes;
-  e = rocprim::exclusive_scan(w.tmp, tb, w.pcount, w.pstart, 0, (size_t)n + 1, rocprim::plus<int32_t>(), s);
-  if (e != hipSuccess) return fail(OT_ERR_HIP, "ot_sparse_adagrad(piece scan): %s", hipGetErrorString(e));
+  OT_TRY(exclusive_scan(w.tmp, w.tmp_bytes, w.pcount, w.pstart, n + 1, s, "ot_sparse_adagrad(piece scan)"));
   const unsigned gp = ceil_div(n + n / PIECE + 1, 256 / tps);
   hipLaunchKernelGGL(piece_sum_kernel, dim3(gp), dim3(256), 0, s, grads, E, w.v_out, w.seg_start, w.pstart, w.nuniq,
                      tps, w.psum);
@@ -322,8 +276,7 @@ extern "C" int ot_sparse_adagrad(float* table, float* accum, int E, int64_t num_
   SparseWs w = carve(workspace, n, E);
   OT_REQUIRE(ws_bytes >= w.total, "ot_sparse_adagrad: workspace too small (%zu < %zu)", ws_bytes, w.total);
   hipStream_t s = (hipStream_t)stream;
-  const int rc = segment_rows(w, E, num_rows, keys, grads, n, s);
-  if (rc != OT_OK) return rc;
+  OT_TRY(segment_rows(w, E, num_rows, keys, grads, n, s));
   const int tps = tps_for(E);
   const unsigned g2 = ceil_div(n, 256 / tps);
   hipLaunchKernelGGL(clip_scale_kernel, dim3(1), dim3(256), 0, s, w.sq_part, (int)g2, clip, w.scale);
@@ -344,8 +297,7 @@ extern "C" int ot_sparse_grad_dense(int E, int64_t num_rows, const int64_t* keys
   SparseWs w = carve(workspace, n, E);
   OT_REQUIRE(ws_bytes >= w.total, "ot_sparse_grad_dense: workspace too small (%zu < %zu)", ws_bytes, w.total);
   hipStream_t s = (hipStream_t)stream;
-  const int rc = segment_rows(w, E, num_rows, keys, grads, n, s);
-  if (rc != OT_OK) return rc;
+  OT_TRY(segment_rows(w, E, num_rows, keys, grads, n, s));
   const int tps = tps_for(E);
   hipLaunchKernelGGL(scatter_rows_kernel, dim3(ceil_div(n, 256 / tps)), dim3(256), 0, s, dense, E, w.k_out,
                      w.seg_start, w.nuniq, w.gsum, tps);
@@ -391,8 +343,7 @@ extern "C" int ot_sparse_prepare(int E, int64_t num_rows, const int64_t* keys, c
   }
   SparseWs w = carve(workspace, n, E);
   OT_REQUIRE(ws_bytes >= w.total, "ot_sparse_prepare: workspace too small (%zu < %zu)", ws_bytes, w.total);
-  const int rc = segment_rows(w, E, num_rows, keys, grads, n, s);
-  if (rc != OT_OK) return rc;
+  OT_TRY(segment_rows(w, E, num_rows, keys, grads, n, s));
   const unsigned g2 = ceil_div(n, 256 / tps_for(E));
   hipLaunchKernelGGL(sum_parts_kernel, dim3(1), dim3(256), 0, s, w.sq_part, (int)g2, sumsq_out);
   OT_LAUNCH_CHECK("ot_sparse_prepare(sumsq)");

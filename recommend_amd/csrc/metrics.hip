@@ -19,12 +19,6 @@ inline int metrics_blocks(int B) {
   return (int)(b < 1 ? 1 : (b > METRICS_MAX_BLOCKS ? METRICS_MAX_BLOCKS : b));
 }
 
-__device__ __forceinline__ double wave_sum_f64(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-
 // One sample of task t: its bin and its terms.  bin = #{j : (double)p > bounds[j]} (bounds ascending, so the
 // count is the first j with !(bounds[j] < p); every compare with a NaN is false: bin 0).
 struct MetricAcc {
@@ -82,9 +76,9 @@ __global__ __launch_bounds__(256) void metrics_update_kernel(const float* __rest
         if (i0 + k < B) metrics_sample(p[i0 + k], y[i0 + k], sb, nb, hist, a);
     }
   }
-  a.se = wave_sum_f64(a.se);
-  a.ae = wave_sum_f64(a.ae);
-  a.bce = wave_sum_f64(a.bce);
+  a.se = wave_sum(a.se);
+  a.ae = wave_sum(a.ae);
+  a.bce = wave_sum(a.bce);
   if ((tid & 63) == 0) {
     red[tid >> 6][0] = a.se;
     red[tid >> 6][1] = a.ae;

@@ -25,11 +25,7 @@
 //   4. per task: AUC_u in double per valid group and the four sums, reduced thread -> wave -> workgroup ->
 //      workgroups in index order through the workspace (no float atomics).  Which thread takes which group depends
 //      on the group's dense index and n only, so agg is also the same under any permutation of the records.
-#include <rocprim/device/device_radix_sort.hpp>
-#include <rocprim/device/device_scan.hpp>
-#include <rocprim/iterator/counting_iterator.hpp>
-
-#include "common.h"
+#include "keyed.h"
 
 namespace ot {
 
@@ -40,26 +36,7 @@ inline int gauc_blocks(int64_t n) {
   return (int)(b < 1 ? 1 : (b > GAUC_MAX_BLOCKS ? GAUC_MAX_BLOCKS : b));
 }
 
-__device__ __forceinline__ double gauc_wave_sum(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-
-// f32 -> u32 with the same order: NaN -> the maximum (above +inf), -0 -> +0, then the sign flip
-__device__ __forceinline__ uint32_t gauc_orderable(float s) {
-  if (s != s) return 0xFFFFFFFFu;
-  const uint32_t u = s == 0.f ? 0u : __float_as_uint(s);
-  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-
-__global__ void gauc_head_flags_kernel(const uint64_t* __restrict__ k, int64_t n, int32_t* flags) {
-  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  flags[i] = (i == 0 || k[i] != k[i - 1]) ? 1 : 0;
-}
-
-// pos = the inclusive scan of flags (1 <= pos[i] <= n).  dense[record] = its group's index; seg_start[0..G] the
+// flags, pos: run_index of the sorted ids (1 <= pos[i] <= n).  dense[record] = its group's index; seg_start[0..G] the
 // groups' first sorted positions (seg_start[G] = n); ids[g] the distinct ids.
 __global__ void gauc_segments_kernel(const uint64_t* __restrict__ k, const int32_t* __restrict__ rec,
                                      const int32_t* __restrict__ flags, const int32_t* __restrict__ pos, int64_t n,
@@ -84,7 +61,7 @@ __global__ void gauc_pack_kernel(const int32_t* __restrict__ dense, const float*
                                  const float* __restrict__ labels, int64_t n, uint64_t* keys) {
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
-  keys[i] = ((uint64_t)(uint32_t)dense[i] << 33) | ((uint64_t)gauc_orderable(scores[i]) << 1) |
+  keys[i] = ((uint64_t)(uint32_t)dense[i] << 33) | ((uint64_t)orderable_f32<true>(scores[i]) << 1) |
             (labels[i] > 0.5f ? 1u : 0u);
 }
 
@@ -179,7 +156,7 @@ __global__ __launch_bounds__(256) void gauc_finalise_kernel(const unsigned long 
   }
 #pragma unroll
   for (int k = 0; k < 4; ++k) {
-    acc[k] = gauc_wave_sum(acc[k]);
+    acc[k] = wave_sum(acc[k]);
     if ((tid & 63) == 0) red[tid >> 6][k] = acc[k];
   }
   __syncthreads();
@@ -219,8 +196,6 @@ struct GaucWs {
   size_t total;
 };
 
-inline size_t gauc_al(size_t x) { return (x + 255) & ~(size_t)255; }
-
 inline int gauc_key_bits(int64_t n) {   // dense indices are below n
   int b = 0;
   while (b < 31 && ((int64_t)1 << b) < n) ++b;
@@ -229,35 +204,24 @@ inline int gauc_key_bits(int64_t n) {   // dense indices are below n
 
 GaucWs gauc_carve(void* base, int T, int64_t n, int group_bits) {
   GaucWs w{};
-  size_t s1 = 0, s2 = 0, s3 = 0;
-  (void)rocprim::radix_sort_pairs(nullptr, s1, (const uint64_t*)nullptr, (uint64_t*)nullptr,
-                                  rocprim::counting_iterator<int32_t>(0), (int32_t*)nullptr, (size_t)n, 0,
-                                  (unsigned)group_bits);
-  rocprim::double_buffer<uint64_t> db((uint64_t*)nullptr, (uint64_t*)nullptr);
-  (void)rocprim::radix_sort_keys(nullptr, s2, db, (size_t)n, 0, (unsigned)gauc_key_bits(n));
-  (void)rocprim::inclusive_scan(nullptr, s3, (int32_t*)nullptr, (int32_t*)nullptr, (size_t)n,
-                                rocprim::plus<int32_t>());
-  w.tmp_bytes = s1 > s2 ? s1 : s2;
-  w.tmp_bytes = w.tmp_bytes > s3 ? w.tmp_bytes : s3;
-  char* p = (char*)base;
-  size_t off = 0;
-  auto take = [&](size_t bytes) { char* r = p ? p + off : nullptr; off += gauc_al(bytes); return (void*)r; };
-  w.dense = (int32_t*)take(n * 4);
-  w.seg_start = (int32_t*)take((n + 1) * 4);
-  w.nuniq = (int32_t*)take(4);
-  w.part = (double*)take((size_t)T * gauc_blocks(n) * 4 * sizeof(double));
-  w.tmp = take(w.tmp_bytes);
-  const size_t shared = off;
-  w.k_out = (uint64_t*)take(n * 8);
-  w.v_out = (int32_t*)take(n * 4);
-  w.flags = (int32_t*)take(n * 4);
-  w.pos = (int32_t*)take(n * 4);
-  const size_t end1 = off;
-  off = shared;
-  w.key_a = (uint64_t*)take(n * 8);
-  w.key_b = (uint64_t*)take(n * 8);
-  w.stat = (unsigned long long*)take(n * 16);
-  w.total = off > end1 ? off : end1;
+  w.tmp_bytes = std::max({sort_iota_bytes<uint64_t>(n, group_bits), sort_keys_bytes<uint64_t>(n, gauc_key_bits(n)),
+                          inclusive_scan_bytes<int32_t>(n)});
+  Carver c(base);
+  w.dense = c.take<int32_t>(n);
+  w.seg_start = c.take<int32_t>(n + 1);
+  w.nuniq = c.take<int32_t>(1);
+  w.part = c.take<double>((size_t)T * gauc_blocks(n) * 4);
+  w.tmp = c.take<char>(w.tmp_bytes);
+  const size_t shared = c.offset();
+  w.k_out = c.take<uint64_t>(n);
+  w.v_out = c.take<int32_t>(n);
+  w.flags = c.take<int32_t>(n);
+  w.pos = c.take<int32_t>(n);
+  c.rewind(shared);
+  w.key_a = c.take<uint64_t>(n);
+  w.key_b = c.take<uint64_t>(n);
+  w.stat = c.take<unsigned long long>(2 * (size_t)n);
+  w.total = c.total();
   return w;
 }
 
@@ -286,30 +250,22 @@ extern "C" int ot_grouped_auc(const int64_t* groups, const float* scores, const 
                  (reinterpret_cast<uintptr_t>(group_stats) & 7) == 0 &&
                  (reinterpret_cast<uintptr_t>(workspace) & 15) == 0,
              "ot_grouped_auc: misaligned operand");
-  const GaucWs w = gauc_carve(workspace, T, n, group_bits);
+  GaucWs w = gauc_carve(workspace, T, n, group_bits);
   OT_REQUIRE(ws_bytes >= w.total, "ot_grouped_auc: workspace too small (%zu < %zu)", ws_bytes, w.total);
   hipStream_t s = (hipStream_t)stream;
   const unsigned g1 = ceil_div(n, 256);
   const int nblk = gauc_blocks(n);
 
   // 1. the groups
-  size_t tb = w.tmp_bytes;
-  hipError_t e = rocprim::radix_sort_pairs(w.tmp, tb, reinterpret_cast<const uint64_t*>(groups), w.k_out,
-                                           rocprim::counting_iterator<int32_t>(0), w.v_out, (size_t)n, 0,
-                                           (unsigned)group_bits, s);
-  if (e != hipSuccess) return fail(OT_ERR_HIP, "ot_grouped_auc(group sort): %s", hipGetErrorString(e));
-  hipLaunchKernelGGL(gauc_head_flags_kernel, dim3(g1), dim3(256), 0, s, w.k_out, n, w.flags);
-  OT_LAUNCH_CHECK("ot_grouped_auc(flags)");
-  tb = w.tmp_bytes;
-  e = rocprim::inclusive_scan(w.tmp, tb, w.flags, w.pos, (size_t)n, rocprim::plus<int32_t>(), s);
-  if (e != hipSuccess) return fail(OT_ERR_HIP, "ot_grouped_auc(scan): %s", hipGetErrorString(e));
+  OT_TRY(sort_iota(w.tmp, w.tmp_bytes, reinterpret_cast<const uint64_t*>(groups), w.k_out, w.v_out, n, group_bits, s,
+                   "ot_grouped_auc(group sort)"));
+  OT_TRY(run_index(w.k_out, n, w.flags, w.pos, w.tmp, w.tmp_bytes, s, "ot_grouped_auc(flags)",
+                   "ot_grouped_auc(scan)"));
   hipLaunchKernelGGL(gauc_segments_kernel, dim3(g1), dim3(256), 0, s, w.k_out, w.v_out, w.flags, w.pos, n, w.dense,
                      w.seg_start, w.nuniq, num_groups, group_ids);
   OT_LAUNCH_CHECK("ot_grouped_auc(segments)");
-  if (group_stats) {
-    e = hipMemsetAsync(group_stats, 0, (size_t)T * n * 3 * sizeof(int64_t), s);
-    if (e != hipSuccess) return fail(OT_ERR_HIP, "ot_grouped_auc(clear): %s", hipGetErrorString(e));
-  }
+  if (group_stats)
+    OT_TRY(hip_status(hipMemsetAsync(group_stats, 0, (size_t)T * n * 3 * sizeof(int64_t), s), "ot_grouped_auc(clear)"));
 
   // 2-4. per binary task
   for (int t = 0; t < T; ++t) {
@@ -318,11 +274,8 @@ extern "C" int ot_grouped_auc(const int64_t* groups, const float* scores, const 
                        labels + (int64_t)t * task_stride, n, w.key_a);
     OT_LAUNCH_CHECK("ot_grouped_auc(pack)");
     rocprim::double_buffer<uint64_t> db(w.key_a, w.key_b);
-    tb = w.tmp_bytes;
-    e = rocprim::radix_sort_keys(w.tmp, tb, db, (size_t)n, 0, (unsigned)gauc_key_bits(n), s);
-    if (e != hipSuccess) return fail(OT_ERR_HIP, "ot_grouped_auc(score sort): %s", hipGetErrorString(e));
-    e = hipMemsetAsync(w.stat, 0, (size_t)n * 16, s);
-    if (e != hipSuccess) return fail(OT_ERR_HIP, "ot_grouped_auc(clear): %s", hipGetErrorString(e));
+    OT_TRY(sort_keys(w.tmp, w.tmp_bytes, db, n, gauc_key_bits(n), s, "ot_grouped_auc(score sort)"));
+    OT_TRY(hip_status(hipMemsetAsync(w.stat, 0, (size_t)n * 16, s), "ot_grouped_auc(clear)"));
     hipLaunchKernelGGL(gauc_stat_kernel, dim3(g1), dim3(256), 0, s, db.current(), n, w.seg_start, w.stat);
     OT_LAUNCH_CHECK("ot_grouped_auc(stat)");
     hipLaunchKernelGGL(gauc_finalise_kernel, dim3(nblk), dim3(256), 0, s, w.stat, w.seg_start, w.nuniq,

@@ -145,14 +145,11 @@ __device__ __forceinline__ float task_loss(float y, float p, bool mse) {
 // when bit t of mse_mask is set, BCE otherwise)
 __global__ __launch_bounds__(256) void bce_fwd_kernel(const float* __restrict__ probs, const float* __restrict__ labels,
                                                       int64_t n, int B, float invB, unsigned mse_mask, float* part) {
-  __shared__ float red[4];
   float s = 0.f;
   for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256)
     s += task_loss(labels[i], probs[i], (mse_mask >> (int)(i / B)) & 1u) * invB;
-  s = wave_sum(s);
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
-  __syncthreads();
-  if (threadIdx.x == 0) part[blockIdx.x] = (red[0] + red[1]) + (red[2] + red[3]);
+  s = block_sum_256(s);
+  if (threadIdx.x == 0) part[blockIdx.x] = s;
 }
 
 __global__ void bce_reduce_kernel(const float* __restrict__ part, int nb, float* loss) {
@@ -180,7 +177,6 @@ __global__ void bce_bwd_kernel(const float* __restrict__ probs, const float* __r
 __global__ __launch_bounds__(256) void loss_z_fwd_kernel(const float* __restrict__ logits, const float* __restrict__ probs,
                                                          const float* __restrict__ labels, int64_t n, int B, float invB,
                                                          unsigned mse_mask, float* part) {
-  __shared__ float red[4];
   float s = 0.f;
   for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
     const float y = labels[i];
@@ -191,10 +187,8 @@ __global__ __launch_bounds__(256) void loss_z_fwd_kernel(const float* __restrict
       s += bce_logits(y, logits[i]) * invB;
     }
   }
-  s = wave_sum(s);
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
-  __syncthreads();
-  if (threadIdx.x == 0) part[blockIdx.x] = (red[0] + red[1]) + (red[2] + red[3]);
+  s = block_sum_256(s);
+  if (threadIdx.x == 0) part[blockIdx.x] = s;
 }
 
 __global__ void loss_z_bwd_kernel(const float* __restrict__ probs, const float* __restrict__ labels,

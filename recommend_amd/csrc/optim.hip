@@ -20,7 +20,6 @@ __device__ __forceinline__ int64_t seg_addr(const int64_t* sg, int64_t e) {
 
 __global__ __launch_bounds__(256) void seg_sumsq_kernel(const float* __restrict__ g, const int64_t* __restrict__ segs,
                                                         int nchunk, float* part) {
-  __shared__ float red[4];
   const int seg = blockIdx.y, ch = blockIdx.x;
   const int64_t* sg = segs + 4 * seg;
   const int64_t n = sg[1] * sg[2];
@@ -30,10 +29,8 @@ __global__ __launch_bounds__(256) void seg_sumsq_kernel(const float* __restrict_
     const float v = g[seg_addr(sg, e)];
     s += v * v;
   }
-  s = wave_sum(s);
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
-  __syncthreads();
-  if (threadIdx.x == 0) part[(int64_t)seg * nchunk + ch] = (red[0] + red[1]) + (red[2] + red[3]);
+  s = block_sum_256(s);
+  if (threadIdx.x == 0) part[(int64_t)seg * nchunk + ch] = s;
 }
 
 __global__ void seg_scale_kernel(const float* __restrict__ part, const int64_t* __restrict__ segs, int nseg, int nchunk,

@@ -20,7 +20,7 @@
 //                     each pass: any n_r), stopping as soon as the threshold digit's bucket is wanted whole; the
 //                     keys >= threshold compacted into LDS (at most 1024), bitonic-sorted descending, written out
 //                     with the padding slots and the count.  n_r <= K skips the select (threshold 0).
-#include "common.h"
+#include "keyed.h"
 
 namespace ot {
 
@@ -31,15 +31,8 @@ struct RankWeights {
   float w[RANK_MAX_T];
 };
 
-// f32 -> u32 with the same order: NaN -> 0 (below -inf), -0 -> +0, then the sign flip
-__device__ __forceinline__ uint32_t rank_orderable(float s) {
-  if (s != s) return 0u;
-  const uint32_t u = s == 0.f ? 0u : __float_as_uint(s);
-  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-
 __device__ __forceinline__ uint64_t rank_key(float f, uint32_t c) {
-  return ((uint64_t)rank_orderable(f) << 32) | (uint64_t)(0xFFFFFFFFu - c);
+  return ((uint64_t)orderable_f32<false>(f) << 32) | (uint64_t)(0xFFFFFFFFu - c);   // NaN -> 0, below -inf
 }
 
 // One thread per candidate.  cnt[R] zeroed by the caller; arrival[c] is written for members only.
@@ -83,22 +76,13 @@ __global__ __launch_bounds__(256) void rank_fuse_kernel(const float* __restrict_
 __global__ __launch_bounds__(256) void rank_scan_kernel(const int32_t* __restrict__ cnt, int R,
                                                         int32_t* __restrict__ start) {
   __shared__ int32_t wtot[4];
-  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+  const int tid = threadIdx.x;
   int32_t carry = 0;
   for (int base = 0; base < R; base += 256) {
     const int r = base + tid;
     const int32_t v = r < R ? cnt[r] : 0;
-    int32_t x = v;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-      const int32_t y = __shfl_up(x, o, 64);
-      if (lane >= o) x += y;
-    }
-    if (lane == 63) wtot[w] = x;
-    __syncthreads();
-    int32_t off = carry;
-    for (int j = 0; j < w; ++j) off += wtot[j];
-    if (r < R) start[r] = off + x - v;
+    const int32_t x = block_scan_256(v, wtot);
+    if (r < R) start[r] = carry + x - v;
     carry += wtot[0] + wtot[1] + wtot[2] + wtot[3];
     __syncthreads();
   }
@@ -127,7 +111,7 @@ __global__ __launch_bounds__(256) void rank_select_kernel(const uint64_t* __rest
   __shared__ int32_t wtot[4];
   __shared__ int32_t sel[3];     // the threshold digit, what is still wanted inside its bucket, the bucket's size
   __shared__ int32_t nlist;
-  const int r = blockIdx.x, tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+  const int r = blockIdx.x, tid = threadIdx.x;
   const int32_t s0 = start[r], n = start[r + 1] - s0;
   const int k = n < K ? n : K;
   const uint64_t* seg = keys + s0;
@@ -155,15 +139,7 @@ __global__ __launch_bounds__(256) void rank_select_kernel(const uint64_t* __rest
       __syncthreads();
       // inclusive scan from the largest digit down: thread t holds digit 255 - t
       const int32_t v = hist[255 - tid];
-      int32_t x = v;
-#pragma unroll
-      for (int o = 1; o < 64; o <<= 1) {
-        const int32_t y = __shfl_up(x, o, 64);
-        if (lane >= o) x += y;
-      }
-      if (lane == 63) wtot[w] = x;
-      __syncthreads();
-      for (int j = 0; j < w; ++j) x += wtot[j];
+      const int32_t x = block_scan_256(v, wtot);
       if (x - v < want && want <= x) {                    // exactly one thread: the k-th key's digit
         sel[0] = 255 - tid;
         sel[1] = want - (x - v);
@@ -219,19 +195,15 @@ struct RankWs {
   size_t total;
 };
 
-inline size_t rank_al(size_t x) { return (x + 255) & ~(size_t)255; }
-
 RankWs rank_carve(void* base, int R, int64_t C) {
   RankWs w{};
-  char* p = (char*)base;
-  size_t off = 0;
-  auto take = [&](size_t bytes) { char* q = p ? p + off : nullptr; off += rank_al(bytes); return (void*)q; };
-  w.keys = (uint64_t*)take((size_t)C * 8);
-  w.fused = (float*)take((size_t)C * 4);
-  w.arrival = (int32_t*)take((size_t)C * 4);
-  w.cnt = (int32_t*)take((size_t)R * 4);
-  w.start = (int32_t*)take(((size_t)R + 1) * 4);
-  w.total = off;
+  Carver c(base);
+  w.keys = c.take<uint64_t>(C);
+  w.fused = c.take<float>(C);
+  w.arrival = c.take<int32_t>(C);
+  w.cnt = c.take<int32_t>(R);
+  w.start = c.take<int32_t>((size_t)R + 1);
+  w.total = c.total();
   return w;
 }
 
@@ -261,10 +233,7 @@ extern "C" int ot_rank_topk(const float* probs, int64_t task_stride, int T, cons
   const RankWs w = rank_carve(workspace, R, C);
   hipStream_t s = (hipStream_t)stream;
   float* fused = fused_out ? fused_out : w.fused;
-  if (R > 0) {
-    hipError_t e = hipMemsetAsync(w.cnt, 0, (size_t)R * 4, s);
-    if (e != hipSuccess) return fail(OT_ERR_HIP, "ot_rank_topk(clear): %s", hipGetErrorString(e));
-  }
+  if (R > 0) OT_TRY(hip_status(hipMemsetAsync(w.cnt, 0, (size_t)R * 4, s), "ot_rank_topk(clear)"));
   if (C > 0) {
     RankWeights wts{};
     for (int t = 0; t < T; ++t) wts.w[t] = weights_host[t];

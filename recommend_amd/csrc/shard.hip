@@ -7,11 +7,7 @@
 // hot ids: a C2-shape batch has ~175k distinct of 516k), so the ids, rows and gradient rows that
 // cross xGMI shrink by that factor; ot_segment_rows_sum pre-sums the repeats' gradients.  The
 // all-to-alls are RCCL (torch.distributed); these kernels are the on-device halves.  All are HBM-bound row moves (16-B accesses), deterministic.
-#include <cstring>
-#include <rocprim/device/device_radix_sort.hpp>
-#include <rocprim/device/device_scan.hpp>
-
-#include "common.h"
+#include "keyed.h"
 
 namespace ot {
 
@@ -37,12 +33,7 @@ __global__ void shard_route_kernel(const int64_t* __restrict__ ids, int64_t n, i
   const uint32_t o = owner_sorted[j];
   if (j == n - 1 || owner_sorted[j + 1] != o) {
     // j is the last of its run; the run starts after the previous run's last element
-    int64_t lo = 0, hi = j;                       // first index with owner_sorted == o
-    while (lo < hi) {
-      const int64_t mid = (lo + hi) >> 1;
-      if (owner_sorted[mid] < o) lo = mid + 1; else hi = mid;
-    }
-    counts[o] = (int32_t)(j - lo + 1);
+    counts[o] = (int32_t)(j - first_owner_ge(owner_sorted, j, o, 0) + 1);
   }
 }
 
@@ -102,8 +93,6 @@ struct RouteWs {
   size_t tmp_bytes, total;
 };
 
-inline size_t al256(size_t x) { return (x + 255) & ~(size_t)255; }
-
 // ---- de-duplicating route (ot_shard_route_unique) -----------------------------------------
 // Sort key of an id: owner in bits 40.., local row + 1 in bits 0..39 (invalid ids: owner 0, 0), so
 // one radix sort orders the ids by owner and brings equal ids together; the stable sort keeps the
@@ -120,14 +109,7 @@ __global__ void ukeys_kernel(const int64_t* __restrict__ ids, int64_t n, int64_t
   pos[i] = (int32_t)i;
 }
 
-// head[j] = 1 where sorted key j starts a run of equal ids
-__global__ void uheads_kernel(const uint64_t* __restrict__ ks, int64_t n, int32_t* head) {
-  const int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (j >= n) return;
-  head[j] = (j == 0 || ks[j] != ks[j - 1]) ? 1 : 0;
-}
-
-// uidx[j] = inclusive count of heads (unique index + 1).  Writes inv (token -> unique), the unique
+// uidx[j] = inclusive count of heads (run_index: unique index + 1).  Writes inv (token -> unique), the unique
 // ids' local rows, the run starts (run_start[U] = n) and per-owner unique counts (run boundaries of
 // the sorted owner field, no atomics).
 __global__ void ufinish_kernel(const uint64_t* __restrict__ ks, const int32_t* __restrict__ order,
@@ -145,11 +127,7 @@ __global__ void ufinish_kernel(const uint64_t* __restrict__ ks, const int32_t* _
   if (j == n - 1) run_start[u + 1] = (int32_t)n;
   const uint64_t o = k >> UKEY_LOCAL_BITS;
   if (j == n - 1 || (ks[j + 1] >> UKEY_LOCAL_BITS) != o) {
-    int64_t lo = 0, hi = j;                       // first sorted index of owner o
-    while (lo < hi) {
-      const int64_t mid = (lo + hi) >> 1;
-      if ((ks[mid] >> UKEY_LOCAL_BITS) < o) lo = mid + 1; else hi = mid;
-    }
+    const int64_t lo = first_owner_ge(ks, j, o, UKEY_LOCAL_BITS);   // first sorted index of owner o
     counts[o] = uidx[j] - (lo > 0 ? uidx[lo - 1] : 0);
   }
 }
@@ -193,12 +171,7 @@ __global__ void seg_piece_sum_kernel(const float* __restrict__ src, const int32_
   const int64_t p = t / c4;
   const int c = 4 * (int)(t % c4);
   if (p >= (int64_t)poff[U - 1] + cnt[U - 1]) return;         // past the last piece
-  int64_t lo = 0, hi = U - 1;                                  // run u: poff[u] <= p < poff[u + 1]
-  while (lo < hi) {
-    const int64_t mid = (lo + hi + 1) >> 1;
-    if (poff[mid] <= p) lo = mid; else hi = mid - 1;
-  }
-  const int64_t u = lo;
+  const int64_t u = last_start_le(poff, U, p);                 // run u: poff[u] <= p < poff[u + 1]
   const int32_t q = (int32_t)(p - poff[u]);
   const int32_t j0 = run_start[u] + q * SEG_PIECE;
   const int32_t j1 = min(run_start[u + 1], j0 + SEG_PIECE);
@@ -231,17 +204,14 @@ struct SegWs {
 
 SegWs carve_seg(void* base, int64_t U, int64_t n, int E) {
   SegWs w{};
-  (void)rocprim::exclusive_scan(nullptr, w.scan_bytes, (int32_t*)nullptr, (int32_t*)nullptr, 0, (size_t)U,
-                                rocprim::plus<int32_t>());
-  char* p = (char*)base;
-  size_t off = 0;
-  auto take = [&](size_t bytes) { char* r = p ? p + off : nullptr; off += al256(bytes); return (void*)r; };
+  w.scan_bytes = exclusive_scan_bytes<int32_t>(U);
+  Carver c(base);
   const int64_t pmax = U + n / SEG_PIECE + 1;
-  w.cnt = (int32_t*)take(U * 4);
-  w.poff = (int32_t*)take(U * 4);
-  w.partial = (float*)take(pmax * E * 4);
-  w.scan_tmp = take(w.scan_bytes);
-  w.total = off;
+  w.cnt = c.take<int32_t>(U);
+  w.poff = c.take<int32_t>(U);
+  w.partial = c.take<float>(pmax * E);
+  w.scan_tmp = c.take<char>(w.scan_bytes);
+  w.total = c.total();
   return w;
 }
 
@@ -254,38 +224,29 @@ struct URouteWs {
 
 URouteWs carve_uroute(void* base, int64_t n) {
   URouteWs w{};
-  (void)rocprim::radix_sort_pairs(nullptr, w.sort_bytes, (uint64_t*)nullptr, (uint64_t*)nullptr, (int32_t*)nullptr,
-                                  (int32_t*)nullptr, (size_t)n, 0, 64);
-  (void)rocprim::inclusive_scan(nullptr, w.scan_bytes, (int32_t*)nullptr, (int32_t*)nullptr, (size_t)n,
-                                rocprim::plus<int32_t>());
-  char* p = (char*)base;
-  size_t off = 0;
-  auto take = [&](size_t bytes) { char* r = p ? p + off : nullptr; off += al256(bytes); return (void*)r; };
-  w.key_in = (uint64_t*)take(n * 8);
-  w.key_out = (uint64_t*)take(n * 8);
-  w.pos_in = (int32_t*)take(n * 4);
-  w.head = (int32_t*)take(n * 4);
-  w.uidx = (int32_t*)take(n * 4);
-  w.sort_tmp = take(w.sort_bytes);
-  w.scan_tmp = take(w.scan_bytes);
-  w.total = off;
+  w.sort_bytes = sort_pairs_bytes<uint64_t>(n, 64);
+  w.scan_bytes = inclusive_scan_bytes<int32_t>(n);
+  Carver c(base);
+  w.key_in = c.take<uint64_t>(n);
+  w.key_out = c.take<uint64_t>(n);
+  w.pos_in = c.take<int32_t>(n);
+  w.head = c.take<int32_t>(n);
+  w.uidx = c.take<int32_t>(n);
+  w.sort_tmp = c.take<char>(w.sort_bytes);
+  w.scan_tmp = c.take<char>(w.scan_bytes);
+  w.total = c.total();
   return w;
 }
 
 RouteWs carve_route(void* base, int64_t n) {
   RouteWs w{};
-  size_t sort_bytes = 0;
-  (void)rocprim::radix_sort_pairs(nullptr, sort_bytes, (uint32_t*)nullptr, (uint32_t*)nullptr, (int32_t*)nullptr,
-                                  (int32_t*)nullptr, (size_t)n, 0, 32);
-  w.tmp_bytes = sort_bytes;
-  char* p = (char*)base;
-  size_t off = 0;
-  auto take = [&](size_t bytes) { char* r = p ? p + off : nullptr; off += al256(bytes); return (void*)r; };
-  w.owner_in = (uint32_t*)take(n * 4);
-  w.owner_out = (uint32_t*)take(n * 4);
-  w.pos_in = (int32_t*)take(n * 4);
-  w.tmp = take(w.tmp_bytes);
-  w.total = off;
+  w.tmp_bytes = sort_pairs_bytes<uint32_t>(n, 32);
+  Carver c(base);
+  w.owner_in = c.take<uint32_t>(n);
+  w.owner_out = c.take<uint32_t>(n);
+  w.pos_in = c.take<int32_t>(n);
+  w.tmp = c.take<char>(w.tmp_bytes);
+  w.total = c.total();
   return w;
 }
 
@@ -310,10 +271,8 @@ extern "C" int ot_shard_route(const int64_t* ids, int64_t n, int64_t num_rows, i
   OT_LAUNCH_CHECK("ot_shard_route(keys)");
   int end_bit = 1;
   while ((1 << end_bit) < world) ++end_bit;
-  size_t tb = w.tmp_bytes;
-  hipError_t e = rocprim::radix_sort_pairs(w.tmp, tb, w.owner_in, w.owner_out, w.pos_in, perm, (size_t)n, 0, end_bit,
-                                           s);
-  if (e != hipSuccess) return fail(OT_ERR_HIP, "ot_shard_route(sort): %s", hipGetErrorString(e));
+  OT_TRY(sort_pairs(w.tmp, w.tmp_bytes, w.owner_in, w.owner_out, w.pos_in, perm, n, end_bit, s,
+                    "ot_shard_route(sort)"));
   hipLaunchKernelGGL(shard_route_kernel, dim3(g), dim3(256), 0, s, ids, n, num_rows, world, w.owner_out, perm,
                      send_local, counts);
   OT_LAUNCH_CHECK("ot_shard_route(route)");
@@ -347,15 +306,10 @@ extern "C" int ot_shard_route_unique(const int64_t* ids, int64_t n, int64_t num_
   OT_LAUNCH_CHECK("ot_shard_route_unique(keys)");
   int end_bit = UKEY_LOCAL_BITS;
   while ((1 << (end_bit - UKEY_LOCAL_BITS)) < world) ++end_bit;
-  size_t sb = w.sort_bytes;
-  hipError_t e = rocprim::radix_sort_pairs(w.sort_tmp, sb, w.key_in, w.key_out, w.pos_in, order, (size_t)n, 0,
-                                           end_bit, s);
-  if (e != hipSuccess) return fail(OT_ERR_HIP, "ot_shard_route_unique(sort): %s", hipGetErrorString(e));
-  hipLaunchKernelGGL(uheads_kernel, dim3(g), dim3(256), 0, s, w.key_out, n, w.head);
-  OT_LAUNCH_CHECK("ot_shard_route_unique(heads)");
-  size_t cb = w.scan_bytes;
-  e = rocprim::inclusive_scan(w.scan_tmp, cb, w.head, w.uidx, (size_t)n, rocprim::plus<int32_t>(), s);
-  if (e != hipSuccess) return fail(OT_ERR_HIP, "ot_shard_route_unique(scan): %s", hipGetErrorString(e));
+  OT_TRY(sort_pairs(w.sort_tmp, w.sort_bytes, w.key_in, w.key_out, w.pos_in, order, n, end_bit, s,
+                    "ot_shard_route_unique(sort)"));
+  OT_TRY(run_index(w.key_out, n, w.head, w.uidx, w.scan_tmp, w.scan_bytes, s, "ot_shard_route_unique(heads)",
+                   "ot_shard_route_unique(scan)"));
   hipLaunchKernelGGL(ufinish_kernel, dim3(g), dim3(256), 0, s, w.key_out, order, w.uidx, n, inv, uniq_local,
                      run_start, counts);
   OT_LAUNCH_CHECK("ot_shard_route_unique(finish)");
@@ -387,9 +341,7 @@ extern "C" int ot_segment_rows_sum_ex(const float* src, const int32_t* order, co
   hipStream_t s = (hipStream_t)stream;
   hipLaunchKernelGGL(seg_piece_count_kernel, dim3(ceil_div(U, 256)), dim3(256), 0, s, run_start, U, w.cnt);
   OT_LAUNCH_CHECK("ot_segment_rows_sum_ex(count)");
-  size_t sb = w.scan_bytes;
-  hipError_t e = rocprim::exclusive_scan(w.scan_tmp, sb, w.cnt, w.poff, 0, (size_t)U, rocprim::plus<int32_t>(), s);
-  if (e != hipSuccess) return fail(OT_ERR_HIP, "ot_segment_rows_sum_ex(scan): %s", hipGetErrorString(e));
+  OT_TRY(exclusive_scan(w.scan_tmp, w.scan_bytes, w.cnt, w.poff, U, s, "ot_segment_rows_sum_ex(scan)"));
   const int64_t pmax = U + n / SEG_PIECE + 1;
   hipLaunchKernelGGL(seg_piece_sum_kernel, dim3(ceil_div(pmax * (E / 4), 256)), dim3(256), 0, s, src, order, run_start,
                      w.cnt, w.poff, U, pmax, E, w.partial, out);

@@ -512,6 +512,51 @@ def test_dense_exchange_matches_sparse(dev):
     assert bool((t2[untouched] == table[untouched]).all()) and bool((a2[untouched] == acc[untouched]).all())
 
 
+@pytest.mark.parametrize('E', [4, 16, 520])
+def test_segment_sums_fixed_order(dev, E):
+    """Both piece-split segmented row sums (ot_segment_rows_sum_ex, and the one inside ot_sparse_grad_dense) add in
+    the order the header promises, bit for bit: pieces of 64 positions in ascending position order from zero, then
+    a run's pieces in order from zero.  The runs sit on both sides of every piece boundary; E = 520 takes the
+    64-thread column loop of the embedding kernels round three times, the last pass partial."""
+    rng = np.random.default_rng(17)
+    num_rows, piece = 16, 64
+    ids = np.array([3, 0, 15, 7, 8, 12, 5])
+    runs = np.array([1, 63, 64, 65, 128, 129, 1000])
+    n = int(runs.sum())
+    assert n == 1450
+    keys2 = rng.permutation(np.repeat(ids, runs)).astype(np.int64)            # interleaved positions
+    keys2 = np.insert(keys2, np.sort(rng.integers(0, n + 1, 5)), [-1, num_rows, -1, -1, num_rows])
+    g2 = rng.standard_normal((n + 5, E)).astype(np.float32)
+    valid = (keys2 >= 0) & (keys2 < num_rows)
+    keys, g = keys2[valid], g2[valid]                                         # the same rows in the same order
+    order = np.argsort(keys, kind='stable').astype(np.int32)                  # by key, positions ascending
+    uk = np.unique(keys)
+    run_start = np.concatenate([[0], np.cumsum([(keys == k).sum() for k in uk])]).astype(np.int32)
+    ref = np.zeros((len(uk), E), np.float32)
+    for u in range(len(uk)):
+        pos = order[run_start[u]:run_start[u + 1]]
+        total = np.zeros(E, np.float32)
+        for p0 in range(0, len(pos), piece):
+            acc = np.zeros(E, np.float32)
+            for i in pos[p0:p0 + piece]:
+                acc = acc + g[i]
+            total = total + acc
+        ref[u] = total
+    assert sorted(np.diff(run_start)) == sorted(runs)
+
+    out = torch.full((len(uk), E), float('nan'), device=dev)
+    K.segment_rows_sum(torch.from_numpy(g).to(dev), torch.from_numpy(order).to(dev), torch.from_numpy(run_start).to(dev),
+                       len(uk), E, out, n=n)
+    assert np.array_equal(out.cpu().numpy().view(np.uint32), ref.view(np.uint32))
+
+    dense = torch.zeros(num_rows, E, device=dev)
+    K.sparse_grad_dense(E, num_rows, torch.from_numpy(keys2).to(dev), torch.from_numpy(g2).to(dev), n + 5, dense,
+                        device=dev)
+    dense = dense.cpu().numpy()
+    assert np.array_equal(dense[uk].view(np.uint32), ref.view(np.uint32))
+    assert not dense[np.setdiff1d(np.arange(num_rows), uk)].view(np.uint32).any()
+
+
 def test_clip_rmsprop(dev):
     rng = np.random.default_rng(4)
     total = 5000
