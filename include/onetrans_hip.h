@@ -691,6 +691,38 @@ int ot_rank_topk(const float* probs, int64_t task_stride, int T, const float* we
                  const int32_t* req, int64_t C, int R, int K, int32_t* top_idx, float* top_score,
                  int32_t* count, float* fused_out, void* workspace, size_t ws_bytes, void* stream);
 
+/* ---- sequence fusion (seqfuse.hip) ------------------------------------------------------------
+ * Timestamp-aware fusion of a sample's behaviour sequences into one token stream: the output-row
+ * entries of the per-sequence projection GEMM's row map, computed per call from the events' times.
+ * Stream-ordered, no allocation, no host sync.
+ *   seqs      nseq HOST descriptors, read at call time and passed to the kernel by value; their order
+ *             is the order of the sequences in the key below.  times: device int64, sample b's L events
+ *             at times + b * stride_b (stride_b >= L); map_off: first entry of the sequence's segment
+ *             in out_rows (the segment offsets ot_seq_rows is given); L may be 0.  sum of L = L_S.
+ *   order     per sample, the stable sort of its L_S events by the key (time, index of the sequence
+ *             in seqs, position in the sequence): a total order, so the ranks are a permutation of
+ *             0 .. L_S-1 for any times (unsorted sequences, ties, all equal).  Times compare as signed
+ *             64-bit integers: INT64_MIN, the value for padding events, sorts first.
+ *   outputs   for event j of sequence i in sample b, with rank its place in that order:
+ *               out_rows[map_off_i + b * L_i + j] = b * row_stride + rank   (row_stride >= L_S)
+ *               rank_out[b * L_S + start_i + j]   = rank   (start_i = L_0 + .. + L_{i-1}; or NULL)
+ *               last_time[b]                      = the sample's largest time           (or NULL)
+ *             No other entry of out_rows is written: the map's -1 padding stays.
+ * 1 <= nseq <= 32, B >= 0, 1 <= L_S <= 4096 (the keys are sorted in LDS, 12 bytes per event),
+ * B * row_stride <= INT32_MAX; anything else, inconsistent descriptors or a workspace below
+ * ot_seq_time_rows_workspace_size return OT_ERR_INVALID_ARG without launching.  B = 0 is a no-op.
+ * The sort needs no scratch memory today: the workspace size is one 256-byte unit for every valid
+ * shape (0 for an invalid one). */
+typedef struct {
+  const int64_t* times; /* device, [B] rows of L times, row stride stride_b */
+  int64_t stride_b;
+  int32_t L;            /* events per sample */
+  int32_t map_off;      /* the sequence's segment offset in out_rows */
+} ot_seq_time;
+size_t ot_seq_time_rows_workspace_size(int B, int nseq, int L_S);
+int ot_seq_time_rows(const ot_seq_time* seqs, int nseq, int B, int L_S, int64_t row_stride, int32_t* out_rows,
+                     int32_t* rank_out, int64_t* last_time, void* workspace, size_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -51,6 +51,14 @@ class RmsEpilogue(ctypes.Structure):
                 ('a_rowmax', c_void_p), ('a_rowmax_n', c_int),
                 ('amax_out', c_void_p), ('rowabs_out', c_void_p), ('rowabs_n', c_int)]
 
+class SeqTime(ctypes.Structure):
+    """``ot_seq_time`` (include/onetrans_hip.h): one sequence's times and its segment of the row map."""
+    _fields_ = [('times', c_void_p), ('stride_b', c_int64), ('L', ctypes.c_int32), ('map_off', ctypes.c_int32)]
+
+
+SEQ_TIME_MAX_L = 4096        # ot_seq_time_rows: events per sample (sorted in LDS)
+SEQ_TIME_MAX_SEQ = 32
+
 P = c_void_p
 I64 = c_int64
 
@@ -160,6 +168,8 @@ SIGNATURES = {
     'ot_grouped_auc': (c_int, [P, P, P, c_int, I64, I64, c_int, c_uint32, P, P, P, P, P, c_size_t, P]),
     'ot_rank_topk_workspace_size': (c_size_t, [c_int, I64, c_int]),
     'ot_rank_topk': (c_int, [P, I64, c_int, P, c_int, P, I64, c_int, c_int, P, P, P, P, P, c_size_t, P]),
+    'ot_seq_time_rows_workspace_size': (c_size_t, [c_int, c_int, c_int]),
+    'ot_seq_time_rows': (c_int, [P, c_int, c_int, c_int, I64, P, P, P, P, c_size_t, P]),
 }
 
 # ABI notes (mirrors include/onetrans_hip.h): the modes/flags above; the only struct is

@@ -107,6 +107,12 @@ class OneTransConfig:
         self.adagrad_epsilon = 1e-7              # build: Keras Adagrad default
         self.rmsprop_rho = 0.9                   # build: Keras RMSprop default (train.py:66 reads rho default)
         self.rmsprop_epsilon = 1e-7              # build: Keras RMSprop default (train.py:68)
+        # build: how the behaviour sequences become the S tokens.  'sep' (the reference, model.py:256-277): whole
+        # sequences concatenated, a learnable [SEP] after each but the last.  'time' (the paper's default,
+        # timestamp-aware): every event interleaved by its time, no [SEP]; each present sequence ``name`` then
+        # needs integer times ``seq_features[name + seq_time_suffix]`` [B, L_name] (DESIGN.md §Sequence fusion)
+        self.seq_fusion = 'sep'
+        self.seq_time_suffix = '_time'
 
     # ------------------------------------------------------------------ helpers
     def to_dict(self) -> Dict:
@@ -143,9 +149,12 @@ class OneTransConfig:
         return sum(self.ns_embedding_dim if n in self.sparse_features else 1 for n in names)
 
     def seq_token_count(self, seq_lens: List[int]) -> int:
-        """L_S = sum(L_i) + one [SEP] after every present sequence i < n-1 (model.py:266-272)."""
+        """L_S = sum(L_i) + one [SEP] after every present sequence i < n-1 (model.py:266-272); no [SEP] under
+        ``seq_fusion='time'``."""
         n = len(self.feature_config['sequence_features'])
-        return int(sum(seq_lens)) + max(0, n - 1) if len(seq_lens) == n else None
+        if len(seq_lens) != n:
+            return None
+        return int(sum(seq_lens)) + (max(0, n - 1) if getattr(self, 'seq_fusion', 'sep') == 'sep' else 0)
 
     def pyramid_schedule(self, total_seq_len: int) -> List[Dict]:
         """Per layer (in_len I_l, keep K_l).  Follows PyramidScheduler.get_layer_config
@@ -276,6 +285,15 @@ def check_pyramid_select(cfg: OneTransConfig) -> None:
     if sel == 'norm' and cfg.dedicated_positions != 'tail':
         raise ValueError("pyramid_select='norm' needs dedicated_positions='tail' (the kept NS rows keep their "
                          "dedicated weights)")
+
+
+def check_seq_fusion(cfg: OneTransConfig) -> None:
+    """``seq_fusion`` is 'sep' (reference: concatenation with [SEP]) or 'time' (timestamp-aware interleave)."""
+    mode = getattr(cfg, 'seq_fusion', 'sep')
+    if mode not in ('sep', 'time'):
+        raise ValueError(f"unknown seq_fusion {mode!r}: expected 'sep' or 'time'")
+    if mode == 'time' and not getattr(cfg, 'seq_time_suffix', '_time'):
+        raise ValueError("seq_fusion='time' needs a non-empty seq_time_suffix")
 
 
 def workload_config(name: str) -> OneTransConfig:

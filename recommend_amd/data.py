@@ -12,6 +12,10 @@
   13 dense floats ``log1p(lognormal(0,1))``, 26 categorical ids
   ``Zipf(1.1) mod cardinality`` and 3 item-id sequences.
 
+* ``seq_times`` — when ``config.seq_fusion == 'time'`` both generators also emit each sequence's event times
+  (``name + config.seq_time_suffix``, int64 ``[B, L_i]``) from a generator of their own, so every other array of a
+  batch is bit-identical to the ``'sep'`` batch of the same seed.
+
 All generators are numpy ``Generator(PCG64)``: same seed => same batch, here and
 on the GPU box.
 """
@@ -39,6 +43,34 @@ def _teacher_labels(rng_seed: int, B: int, tasks: List[str], signal: np.ndarray)
     return labels
 
 
+TIME_ORIGIN = 1_700_000_000        # epoch seconds of the synthetic event times
+
+
+def seq_times(seed: int, B: int, names: List[str], lens: List[int], suffix: str = '_time') -> Dict[str, np.ndarray]:
+    """Synthetic event times for ``seq_fusion='time'``: {name + suffix: int64 [B, L]} epoch seconds.  Each
+    sequence ascends in time except for a few swapped neighbours (real logs arrive slightly out of order), and
+    all sequences draw from one short span, so times tie within and across sequences.  The generator is its own
+    (seeded by ``seed``): the other arrays of a batch do not depend on whether times are drawn."""
+    rng = np.random.Generator(np.random.PCG64([int(seed), 0x74696D65]))
+    span = max(4, 2 * int(sum(lens)))
+    rows = np.arange(B)
+    out = {}
+    for name, L in zip(names, lens):
+        t = np.sort(rng.integers(0, span, size=(B, L)), axis=1)
+        for _ in range(max(1, L // 16) if L >= 2 else 0):
+            i = rng.integers(0, L - 1, size=B)
+            t[rows, i], t[rows, i + 1] = t[rows, i + 1].copy(), t[rows, i].copy()
+        out[name + suffix] = (TIME_ORIGIN + t).astype(np.int64)
+    return out
+
+
+def _add_times(seq: Dict[str, np.ndarray], config: OneTransConfig, seed: int) -> None:
+    if getattr(config, 'seq_fusion', 'sep') != 'time' or not seq:
+        return
+    B = next(iter(seq.values())).shape[0]
+    seq.update(seq_times(seed, B, list(seq), [v.shape[1] for v in seq.values()], config.seq_time_suffix))
+
+
 def create_sample_batch(batch_size: int, config: OneTransConfig, seq_lens: Optional[List[int]] = None,
                         seed: int = 1000) -> Batch:
     """data_loader.py:301-329 with the deviations listed in the module docstring."""
@@ -56,6 +88,7 @@ def create_sample_batch(batch_size: int, config: OneTransConfig, seq_lens: Optio
     lens = seq_lens or getattr(config, '_seq_lens', None) or [10] * len(fc['sequence_features'])
     for name, L in zip(fc['sequence_features'], lens):
         seq[name] = rng.random((B, L, config.seq_feature_dim), dtype=np.float32)
+    _add_times(seq, config, seed)
     trng = np.random.Generator(np.random.PCG64(7))
     nsmat = np.concatenate([ns[n] for n in config.ns_feature_names() if n in ns], axis=1)
     a = trng.normal(size=(nsmat.shape[1], 2)) / np.sqrt(nsmat.shape[1])
@@ -98,6 +131,7 @@ def criteo_batch(batch_size: int, config: OneTransConfig, seq_lens: Optional[Lis
     vocab = config.seq_item_vocab
     for name, L in zip(fc['sequence_features'], lens):
         seq[name] = ((rng.zipf(1.1, size=(B, L)) - 1) % vocab).astype(np.int64)
+    _add_times(seq, config, seed)
     if teacher == 'dense':
         signal = dense_signal
     elif teacher != 'ids':

@@ -25,6 +25,7 @@ import numpy as np
 from .config import OneTransConfig
 
 Batch = tuple
+TIME_PAD = np.iinfo(np.int64).min      # the time of a padding event: first in the time order (seq_fusion='time')
 
 
 class FeatureProcessor:
@@ -89,6 +90,22 @@ class SequenceProcessor:
     def __init__(self, config: OneTransConfig, width: int = 64):
         self.max_seq_len = config.max_seq_len
         self.width = width
+        self.time_suffix = getattr(config, 'seq_time_suffix', '_time')
+
+    def is_time_key(self, name: str, names) -> bool:
+        """Is ``name`` the companion times of a sequence in ``names`` (``seq + seq_time_suffix``, the input of
+        ``seq_fusion='time'``)?"""
+        sfx = self.time_suffix
+        return bool(sfx) and name.endswith(sfx) and name[:-len(sfx)] in names
+
+    def process_times(self, times) -> np.ndarray:
+        """``process_sequence`` for a sequence's event times: the last max_seq_len as int64, left-padded with
+        TIME_PAD (INT64_MIN) so that padding events sort first under ``seq_fusion='time'``."""
+        return self.pad_times([times])[0]
+
+    def pad_times(self, seqs: Sequence[np.ndarray]) -> np.ndarray:
+        """``pad_batch`` for event times: [B, max_seq_len] int64, left-padded with TIME_PAD."""
+        return self.pad_batch(seqs, dtype=np.int64, pad_value=TIME_PAD, event_shape=())
 
     def process_sequence(self, sequence_data: np.ndarray, sequence_type: Optional[str] = None) -> np.ndarray:
         """:75-94: keep the last max_seq_len events, left-pad with zeros (an empty sequence: float64
@@ -107,18 +124,19 @@ class SequenceProcessor:
         """:96-101: process_sequence on each behaviour sequence, keyed by its type."""
         return {t: self.process_sequence(s, t) for t, s in sequences.items()}
 
-    def pad_batch(self, seqs: Sequence[np.ndarray], dtype=np.float32) -> np.ndarray:
+    def pad_batch(self, seqs: Sequence[np.ndarray], dtype=np.float32, pad_value=0, event_shape=None) -> np.ndarray:
         """process_sequence over a batch, vectorised into one [B, max_seq_len, ...] array (event
-        features [., width] or item ids [.])."""
+        features [., width] or item ids [.]).  ``pad_value`` fills the left padding (event times: TIME_PAD, see
+        ``pad_times``); ``event_shape`` fixes one event's shape when every sequence may be empty."""
         L = self.max_seq_len
-        tail = None
+        tail = event_shape
         for s in seqs:
             s = np.asarray(s)
-            if len(s):
+            if len(s) and tail is None:
                 tail = s.shape[1:]
                 break
         tail = tail if tail is not None else (self.width,)
-        out = np.zeros((len(seqs), L) + tuple(tail), dtype=dtype)
+        out = np.full((len(seqs), L) + tuple(tail), pad_value, dtype=dtype)
         for b, s in enumerate(seqs):
             s = np.asarray(s)
             n = min(len(s), L)
@@ -212,7 +230,9 @@ class OneTransDataset:
                 ns[name] = fp.process_categorical_feature(name, x, one_hot=False).reshape(-1, 1)
             else:
                 ns[name] = np.asarray(fp.process_numerical_feature(name, x), dtype=np.float32).reshape(-1, 1)
-        seq = {name: self.sequence_processor.pad_batch([lst[i] for i in idx]) for name, lst in self.seq_data.items()}
+        sp = self.sequence_processor
+        seq = {name: (sp.pad_times if sp.is_time_key(name, self.seq_data) else sp.pad_batch)([lst[i] for i in idx])
+               for name, lst in self.seq_data.items()}
         lab = {t: np.asarray(v, dtype=np.float32)[idx].reshape(-1, 1) for t, v in self.labels.items()}
         return ns, seq, lab
 

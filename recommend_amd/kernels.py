@@ -614,6 +614,28 @@ def rank_topk(probs, task_stride, T, weights, mode, req, C, R, K, top_idx, top_s
         _probe.end('rank', 0.0, ev)
 
 
+def seq_time_descs(seqs):
+    """The host descriptor array of ``seq_time_rows``: ``seqs`` = [(times, stride_b, L, map_off)], ``times`` a device
+    int64 tensor (or (tensor, element offset)).  Build it once for buffers that persist (OneTransModel's plan)."""
+    arr = (_lib.SeqTime * max(1, len(seqs)))()
+    for k, (t, stride_b, L, off) in enumerate(seqs):
+        arr[k] = _lib.SeqTime(ptr(t), int(stride_b), int(L), int(off))
+    return arr
+
+
+def seq_time_rows(descs, nseq: int, B: int, L_S: int, row_stride: int, out_rows, rank_out=None, last_time=None,
+                  device=None) -> None:
+    """ot_seq_time_rows: per sample the stable order of its L_S events by (time, sequence, position); writes
+    out_rows[map_off_i + b L_i + j] = b row_stride + rank, optionally ``rank_out`` [B, L_S] int32 (concatenation
+    order) and ``last_time`` [B] int64.  ``descs``: seq_time_descs(...)."""
+    ws = workspace(size('ot_seq_time_rows_workspace_size', B, nseq, L_S), device)
+    ev = _probe.begin() if _probe is not None else None
+    call('ot_seq_time_rows', ctypes.cast(descs, ctypes.c_void_p), nseq, B, L_S, row_stride, ptr(out_rows),
+         ptr(rank_out), ptr(last_time), ptr(ws), ws.numel(), stream())
+    if ev is not None:
+        _probe.end('embedding', 0.0, ev)
+
+
 def task_loss_logits_fwd(logits, probs, labels, T, B, loss, device=None, mse_mask: int = 0) -> None:
     """Σ_task loss (train.py:78-93) as Keras 2.12 computes it on sigmoid heads: BCE from the logits, MSE
     (bits of ``mse_mask``) from the probabilities."""

@@ -30,7 +30,7 @@ from . import kernels as K
 from ._lib import (OT_AX_BF16, OT_AX_BF16_RMSNORM, OT_AX_GELU, OT_AX_RMSNORM, OT_EPI_ACCUMULATE, OT_EPI_AUX_BF16, OT_EPI_BIAS,
                    OT_EPI_C_BF16, OT_EPI_DROPOUT, OT_EPI_GELU_BWD, OT_EPI_RESIDUAL, OT_EPI_RMSNORM_BWD,
                    OT_EPI_ROW_RSTD, OT_EPI_ROWDOT, OT_GEMM_NN, OT_GEMM_NT, OT_WG_D_BF16, NS_FIELD_BYTES)
-from .config import OneTransConfig, check_pyramid_select, get_model_config
+from .config import OneTransConfig, check_pyramid_select, check_seq_fusion, get_model_config
 from .layout import TILE, FlatLayout, RowMap, build_map, head_map, identity_map, layer_maps, round_up
 from .params import init_params, ns_table_offsets
 
@@ -62,7 +62,7 @@ class _Tokenize(torch.autograd.Function):
             sm = plan['seq_map'].to(dev)
             A, lda = plan['seq_A'], m.config.seq_feature_dim
             K.gemm(OT_GEMM_NT, A, lda, lda, plan['seq_in'], m.pT('tok.seq.kernel'), lda * d, lda, d, sm['tile_group'],
-                   plan['seq_map'].ntiles, x0, d, sm['rows'][0], bias=m.p('tok.seq.bias'), bias_gstride=d,
+                   plan['seq_map'].ntiles, x0, d, _seq_out_rows(plan, sm), bias=m.p('tok.seq.bias'), bias_gstride=d,
                    epi=OT_EPI_BIAS, m_rows=plan['seq_M'], bimg=m.bimg('tok.seq.kernel'))
         if plan['n_sep'] > 0:                                   # model.py:270-272
             K.fill_rows(x0, d, plan['sep_rows'], plan['n_sep'], m.p('tok.sep'), d)
@@ -110,14 +110,15 @@ class _Tokenize(torch.autograd.Function):
         E = m.config.seq_feature_dim
         if plan['seq_map'] is not None:
             sm = plan['seq_map'].to(dev)
-            K.wgrad(plan['seq_A'], E, plan['seq_in'], dx0, d, sm['rows'][0], E, d, sm,
+            xrows = _seq_out_rows(plan, sm)
+            K.wgrad(plan['seq_A'], E, plan['seq_in'], dx0, d, xrows, E, d, sm,
                     plan['seq_map'].chunks.shape[0], plan['nseq'], m.g('tok.seq.kernel'), E * d,
                     m.g('tok.seq.bias'), d, accumulate=acc, device=dev, m_rows=plan['seq_M'],
                     rowmap=plan['seq_map'])
             if plan['seq_ids'] is not None:
                 M = plan['seq_M']
                 demb = torch.empty(M, E, device=dev)
-                K.gemm(OT_GEMM_NT, dx0, d, d, sm['rows'][0], m.p('tok.seq.kernel'), E * d, d, E, sm['tile_group'],
+                K.gemm(OT_GEMM_NT, dx0, d, d, xrows, m.p('tok.seq.kernel'), E * d, d, E, sm['tile_group'],
                        plan['seq_map'].ntiles, demb, E, sm['rows'][1], m_rows=plan['seq_M'])
                 # a sharded table takes its gradient rows along the lookup's all-to-all route
                 keys = plan['seq_route'] if 'emb.seq_item' in m.sharded else plan['seq_ids']
@@ -130,6 +131,13 @@ class _Tokenize(torch.autograd.Function):
             m.g('tok.sep').zero_()
         m.join_side_stream()          # last backward of the graph: every block's weight gradients are in
         return None, None, None
+
+
+def _seq_out_rows(plan, sm):
+    """x0 rows of the sequence projection's row map: the static map (``seq_fusion='sep'``), or under 'time' the
+    plan's per-call copy that ot_seq_time_rows filled from this call's timestamps (``_plan``)."""
+    rows = plan.get('seq_rows_t')
+    return rows if rows is not None else sm['rows'][0]
 
 
 def layer_seed(seed: int, b0: int, I: int, d: int) -> int:
@@ -731,6 +739,8 @@ class OneTransModel(nn.Module):
         if cfg.hidden_dim % cfg.num_heads or (cfg.hidden_dim // cfg.num_heads) not in (16, 32, 64, 128):
             raise ValueError('head_dim must be 16, 32, 64 or 128')
         check_pyramid_select(cfg)
+        check_seq_fusion(cfg)
+        self.time_fusion = getattr(cfg, 'seq_fusion', 'sep') == 'time'
         # compute_dtype (build knob): 'fp32' (the reference's arithmetic: split or f32 GEMMs, ``matmul`` below),
         # 'bf16', or 'fp8attn' = BASELINE configs[4]'s attention on
         # block-scaled fp8 MFMA (forward QK^T and PV; the backward recomputes in the GEMM mode's precision from
@@ -1050,6 +1060,7 @@ class OneTransModel(nn.Module):
         ns_present = tuple(n for n in cfg.ns_feature_names() if n in ns)
         id_seq = bool(cfg.seq_item_vocab) and bool(present) and not torch.is_floating_point(torch.as_tensor(seq[present[0][1]]))
         key = (B, tuple(present), ns_present, id_seq)
+        times = self._seq_times(seq, present, B) if self.time_fusion and present else None
         plan = self._plans.get(key)
         if plan is None:
             plan = self._build_plan(B, present, ns_present, id_seq)
@@ -1064,6 +1075,13 @@ class OneTransModel(nn.Module):
                 plan['ids_buf'].copy_(torch.cat([ns[n].reshape(B, 1).to(dev, torch.int64)
                                                  for n in plan['sparse_names']], 1))
         if plan['seq_map'] is not None:
+            if self.time_fusion:
+                # timestamp-aware fusion: stage the events' times and order each sample's events on the device;
+                # the projection GEMM, its weight gradient and the embedding dgrad read the resulting x0 rows
+                for buf, t in zip(plan['time_bufs'], times):
+                    buf.copy_(t)
+                K.seq_time_rows(plan['time_descs'], len(present), B, plan['L_S'], plan['L0'], plan['seq_rows_t'],
+                                rank_out=plan['seq_rank'], last_time=plan['last_time'], device=dev)
             if id_seq and 'emb.seq_item' in self.sharded:
                 # row-sharded table: the rows arrive through the all-to-all lookup in token order, and
                 # the projection reads them through the static (identity) row map; the ids are staged
@@ -1099,19 +1117,44 @@ class OneTransModel(nn.Module):
                 plan['seq_ids'] = None
         return plan
 
+    def _seq_times(self, seq, present, B) -> List[torch.Tensor]:
+        """The present sequences' event times (``seq_fusion='time'``): ``seq[name + seq_time_suffix]``, an integer
+        [B, L_name] host array or device tensor each."""
+        sfx = self.config.seq_time_suffix
+        out = []
+        for (_, n, L) in present:
+            if n + sfx not in seq:
+                raise ValueError(f"seq_fusion='time': sequence {n!r} has no times ({n + sfx!r} is missing from "
+                                 'seq_features)')
+            t = seq[n + sfx]
+            t = t if isinstance(t, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(t))
+            if t.is_floating_point() or t.is_complex() or t.dtype == torch.bool:
+                raise TypeError(f'seq_fusion=\'time\': the times of sequence {n!r} ({n + sfx!r}) are {t.dtype}; '
+                                'integer timestamps are expected (they are widened to int64)')
+            if tuple(t.shape) != (B, L):
+                raise ValueError(f"seq_fusion='time': the times of sequence {n!r} ({n + sfx!r}) have shape "
+                                 f'{tuple(t.shape)}, expected {(B, L)}')
+            out.append(t)
+        return out
+
     def _build_plan(self, B, present, ns_present, id_seq):
         cfg = self.config
         d = cfg.hidden_dim
         dev = self.device
         nseq_cfg = len(cfg.feature_config['sequence_features'])
         plan = {'B': B, 'gen': 0}
-        # ---- sequence token positions (model.py:259-277)
+        if self.time_fusion and present and id_seq and 'emb.seq_item' in self.sharded:
+            raise NotImplementedError("seq_fusion='time' with a row-sharded emb.seq_item table is not supported: the "
+                                      "sharded lookup delivers rows through a static token-order route; use "
+                                      "table_sharding='none' or seq_fusion='sep'")
+        # ---- sequence token positions (model.py:259-277; 'time': the concatenation without [SEP] — the places
+        # the events take when their times reproduce it; the per-call order comes from ot_seq_time_rows)
         pos = 0
         seq_groups, sep_pos = [], []
         for (i, n, L) in present:
             seq_groups.append((i, pos, L))
             pos += L
-            if i < nseq_cfg - 1:
+            if i < nseq_cfg - 1 and not self.time_fusion:
                 sep_pos.append(pos)
                 pos += 1
         L_S = pos
@@ -1150,6 +1193,18 @@ class OneTransModel(nn.Module):
             plan['seq_in'] = seq_in
             if not id_seq:
                 plan['seq_buf'] = torch.empty(cmp_off, cfg.seq_feature_dim, device=dev)
+            if self.time_fusion:
+                if L_S > _lib.SEQ_TIME_MAX_L:
+                    raise ValueError(f"seq_fusion='time': {L_S} events per sample, at most {_lib.SEQ_TIME_MAX_L}")
+                # persistent per-call buffers (restaged by every _plan; the backward's generation guard covers
+                # them): the times, the map's x0 rows (a copy of the static rows, whose -1 padding the kernel
+                # never touches), each event's rank in concatenation order and the samples' latest time
+                plan['time_bufs'] = [torch.empty(B, L, dtype=torch.int64, device=dev) for (_, _, L) in seq_groups]
+                plan['time_descs'] = K.seq_time_descs([(t, L, L, off) for t, (_, _, L), off
+                                                       in zip(plan['time_bufs'], seq_groups, offs)])
+                plan['seq_rows_t'] = torch.from_numpy(rm.rows[0].copy()).to(dev)
+                plan['seq_rank'] = torch.empty(B, L_S, dtype=torch.int32, device=dev)
+                plan['last_time'] = torch.empty(B, dtype=torch.int64, device=dev)
         else:
             plan['seq_map'] = None
         # ---- NS fields (model.py:243-253)

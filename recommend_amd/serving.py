@@ -24,6 +24,9 @@ Cross-request reuse (``extend_requests``): new behaviours appended to the LAST c
 extend the S side at its end, so with no pruning before the last layer only the new tokens are computed
 (their queries over the cached K/V).  Appends anywhere else shift later positions (later sequences,
 [SEP] tokens, position-grouped weights) and need a full stage-I re-encode; that case raises.
+Under ``seq_fusion='time'`` the S side is ordered by event time and has no [SEP]: new events of any present
+sequence land at its end as long as they are later than the request's cached latest event
+(``RequestCache.last_time``), so every behaviour can extend the cache.
 """
 
 from __future__ import annotations
@@ -43,9 +46,12 @@ class RequestCache:
     """Stage-I output for R requests: per layer the S-side qkv rows [R*Ic, 3d] (k at col d, v at 2d)
     and Ic, the number of S tokens in that layer's input."""
 
-    def __init__(self, R: int, L_S: int, layers: List[Dict], present=()):
+    def __init__(self, R: int, L_S: int, layers: List[Dict], present=(), last_time: Optional[torch.Tensor] = None):
         self.R, self.L_S, self.layers = R, L_S, layers
         self.present = tuple(present)          # sequence names present in the requests, config order
+        # seq_fusion='time': each request's latest event time, [R] int64 on the device (ot_seq_time_rows);
+        # extend_requests appends only events after it
+        self.last_time = last_time
 
 
 class OneTransServer:
@@ -158,12 +164,14 @@ class OneTransServer:
             x, qkv = self._block(l, x, R, s, kS, 0, e['I'], attn)
             layers.append({'Ic': s, 'kv': qkv})
         present = [n for n in cfg.feature_config['sequence_features'] if n in seq_features]
-        return RequestCache(R, L_S, layers, present)
+        last_time = plan['last_time'].clone() if m.time_fusion else None
+        return RequestCache(R, L_S, layers, present, last_time)
 
     # ------------------------------------------------------------------ cross-request append
     @torch.no_grad()
     @K.in_model_precision
-    def extend_requests(self, cache: RequestCache, seq_name: str, new_events: torch.Tensor) -> RequestCache:
+    def extend_requests(self, cache: RequestCache, seq_name: str, new_events: torch.Tensor,
+                        new_times: Optional[torch.Tensor] = None) -> RequestCache:
         """Cross-request KV cache (paper §3.5.1): the requests' newest behaviours ``new_events``
         ([R, dL, 64] features or [R, dL] ids) are appended to sequence ``seq_name`` and only the new
         S tokens are computed, their queries attending over the cached K/V (ot_attn_fwd_cached).
@@ -172,14 +180,25 @@ class OneTransServer:
         the end of the S side and shift nothing: ``seq_name`` must be the last configured sequence
         (no [SEP] follows it, model.py:270-272) and present in the requests, and no layer before the
         last may prune (a pyramid keep would move with the length).  Weight groups are functions of the
-        absolute position, which the old tokens keep."""
+        absolute position, which the old tokens keep.
+
+        ``seq_fusion='time'``: the stream is ordered by time, so new events of ANY present sequence land at its
+        end — when, per request, every time of ``new_times`` ([R, dL] integers) is later than the request's cached
+        latest time (``cache.last_time``).  A time equal to it is accepted only for the last configured sequence
+        (only there is the tie certain to sort last: the key is (time, sequence, position)).  Checked with one
+        small read-back before anything is launched; a violation raises ValueError.  ``new_times`` is ignored
+        under 'sep'."""
         from .model import _Tokenize
         m = self.m
         cfg = m.config
         d, H = cfg.hidden_dim, cfg.num_heads
         hd = d // H
         seqs = cfg.feature_config['sequence_features']
-        if seq_name != seqs[-1] or seq_name not in cache.present:
+        if m.time_fusion:
+            if seq_name not in seqs or seq_name not in cache.present:
+                raise ValueError(f'extend_requests: {seq_name!r} is not a configured sequence present in the cached '
+                                 'requests')
+        elif seq_name != seqs[-1] or seq_name not in cache.present:
             raise ValueError(f'extend_requests: only the last configured sequence ({seqs[-1]!r}), present in the '
                              'cached requests, can grow without shifting earlier positions')
         old = self.schedule(cache.L_S)
@@ -187,11 +206,16 @@ class OneTransServer:
             raise ValueError('extend_requests: a pyramid keep before the last layer depends on the length; '
                              're-encode instead')
         R = cache.R
-        plan = m._plan({}, {seq_name: new_events})
+        feats = {seq_name: new_events}
+        if m.time_fusion:
+            feats[seq_name + cfg.seq_time_suffix] = self._check_new_times(cache, seq_name, new_events, new_times)
+        plan = m._plan({}, feats)
         if plan['B'] != R:
             raise ValueError(f'extend_requests: {plan["B"]} rows of new events for {R} cached requests')
         dL = plan['L_S']
+        # 'time': the new events among themselves are ordered by the same kernel (one sequence)
         x0 = _Tokenize.apply(m.flat, m, plan)                             # [R*(dL+L_NS), d], no [SEP]
+        last_time = plan['last_time'].clone() if m.time_fusion else None
         x = x0.view(R, dL + cfg.num_ns_tokens, d)[:, :dL].reshape(R * dL, d)
         new = self.schedule(cache.L_S + dL)
         req = torch.arange(R, dtype=torch.int32, device=x.device)
@@ -210,7 +234,34 @@ class OneTransServer:
             x, qkv = self._block(l, x, R, dL, dL if keep == dL else 0, Ic, e_new['I'], attn)
             kv = qkv if Ic == 0 else torch.cat([lay['kv'].view(R, Ic, 3 * d), qkv.view(R, dL, 3 * d)], 1)
             layers.append({'Ic': Ic + dL, 'kv': kv.reshape(R * (Ic + dL), 3 * d)})
-        return RequestCache(R, cache.L_S + dL, layers, cache.present)
+        return RequestCache(R, cache.L_S + dL, layers, cache.present, last_time)
+
+    def _check_new_times(self, cache: RequestCache, seq_name: str, new_events, new_times) -> torch.Tensor:
+        """``extend_requests`` under seq_fusion='time': the new events' times as a device int64 [R, dL] tensor,
+        after checking that they sort behind everything cached (one read-back of a flag)."""
+        cfg = self.m.config
+        if new_times is None:
+            raise ValueError(f"extend_requests: seq_fusion='time' needs new_times for {seq_name!r}")
+        if cache.last_time is None:
+            raise ValueError('extend_requests: the request cache holds no times (it was not encoded under '
+                             "seq_fusion='time')")
+        t = new_times if isinstance(new_times, torch.Tensor) else torch.as_tensor(new_times)
+        if t.is_floating_point() or t.dtype == torch.bool:
+            raise TypeError(f'extend_requests: new_times are {t.dtype}; integer timestamps are expected')
+        want = tuple(torch.as_tensor(new_events).shape[:2])
+        if tuple(t.shape) != want or t.shape[0] != cache.R or t.shape[1] < 1:
+            raise ValueError(f'extend_requests: new_times of {seq_name!r} have shape {tuple(t.shape)}, expected '
+                             f'{(cache.R,) + want[1:]}')
+        t = t.to(self.m.device, torch.int64)
+        first = t.min(dim=1).values
+        tie_ok = seq_name == cfg.feature_config['sequence_features'][-1]
+        bad = (first < cache.last_time) if tie_ok else (first <= cache.last_time)
+        if bool(bad.any()):
+            raise ValueError(f'extend_requests: {int(bad.sum())} request(s) have a new {seq_name!r} event '
+                             + ('earlier than' if tie_ok else 'not later than')
+                             + ' their cached latest event; it would not land at the end of the time-ordered '
+                             'stream (re-encode instead)')
+        return t
 
     # ------------------------------------------------------------------ stage II
     def _stage2(self, who: str, cache: RequestCache, req: torch.Tensor, non_seq_features: Dict[str, torch.Tensor]):
@@ -342,7 +393,10 @@ class OneTransInferenceEngine:
         non_seq.update(item_features)
         non_seq.update(context_features)
         sp = SequenceProcessor(self.config)
-        seq = {k: sp.process_sequence(np.asarray(v)) for k, v in sequence_features.items()}
+        # a sequence's companion times (name + seq_time_suffix) are left-padded with INT64_MIN, not zeros: padding
+        # events sort first in the time-ordered stream
+        seq = {k: sp.process_times(v) if sp.is_time_key(k, sequence_features) else sp.process_sequence(np.asarray(v))
+               for k, v in sequence_features.items()}
         return non_seq, seq
 
     def _predict(self, non_seq, seq):
