@@ -398,6 +398,23 @@ int ot_attn_bwd_amax(const float* qkv, int64_t ld, const float* out, const float
 int ot_attn_fwd_cached(const float* qkv, int64_t ld, const float* kv_cache, int64_t ldc, const int32_t* req,
                        int C, int H, int Ic, int n, int Kq, int head_dim, float* out, void* stream);
 
+/* Request-grouped training: the cached attention with a backward.  ot_attn_fwd_cached_lse is
+ * ot_attn_fwd_cached (same out, bit for bit) that also writes lse [C, H, Kq] in ot_attn_fwd's convention
+ * (natural log of the softmax denominator of the whole row: cached keys and own rows).
+ * ot_attn_bwd_cached: req_start [R+1] gives request r's candidates [req_start[r], req_start[r+1]) (candidates
+ * sorted by request).  dqkv [C*n, ld]: dq on the Kq kept rows of each candidate only (the other rows' q columns
+ * are not written), dk | dv on all n rows.  dkv_cache [R*Ic, ldc] (dK at col 0, dV at col d): the sum over the
+ * request's candidates in candidate order, one writer per element (no atomics; bit-identical from run to run);
+ * accumulate 0 writes it (zeros for a request without candidates), 1 adds to what is there.  Native f32 MFMA.
+ * workspace: ot_attn_bwd_cached_workspace_size bytes. */
+int ot_attn_fwd_cached_lse(const float* qkv, int64_t ld, const float* kv_cache, int64_t ldc, const int32_t* req,
+                           int C, int H, int Ic, int n, int Kq, int head_dim, float* out, float* lse, void* stream);
+size_t ot_attn_bwd_cached_workspace_size(int R, int C, int H, int Ic, int n, int Kq, int head_dim);
+int ot_attn_bwd_cached(const float* qkv, int64_t ld, const float* kv_cache, int64_t ldc, const int32_t* req_start,
+                       int R, int C, int H, int Ic, int n, int Kq, int head_dim, const float* out, const float* dout,
+                       const float* lse, float* dqkv, float* dkv_cache, int accumulate, void* workspace,
+                       size_t ws_bytes, void* stream);
+
 /* ---- pyramid query selection (pyramid.hip) -----------------------------------------------
  * Replaces PyramidScheduler.get_layer_config + tf.gather (model.py:287-302, 356, 371): per sample,
  * keep the K of I tokens with the largest key (score[b*I+p] * score_sign, ties to the later

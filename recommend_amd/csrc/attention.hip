@@ -1690,7 +1690,8 @@ __global__ __launch_bounds__(256) void attn_fwd_small_kernel(AttnArgs p) {
 // Absolute positions: cache rows 0..Ic-1, N rows Ic..Ic+n-1; query j sits at Ic + n - Kq + j, so
 // every cached key is visible and the causal mask only touches the N-side key blocks.  Same
 // orientation and online softmax as attn_fwd_kernel; key rows come from two sources, so each lane
-// resolves its key row's address (one pointer per lane per key block).  Forward only (no lse).
+// resolves its key row's address (one pointer per lane per key block).  ot_attn_fwd_cached writes no lse
+// (serving); ot_attn_fwd_cached_lse (request-grouped training) runs the same kernel with the lse output set.
 struct AttnCachedArgs {
   const float* qkv; int64_t ld;            // N-side rows [C*n, ld]: q | k | v
   const float* kc; const float* vc; int64_t ldc;   // cached S-side K / V rows [R*Ic, ldc]
@@ -1698,6 +1699,7 @@ struct AttnCachedArgs {
   float* out;                              // [C*Kq, d]
   int C, H, Ic, n, Kq, d;
   float scale;
+  float* lse;                              // [C, H, Kq] natural-log row statistics for the backward, or null
 };
 
 template <int HD>
@@ -1803,6 +1805,207 @@ __global__ __launch_bounds__(256) void attn_fwd_cached_kernel(AttnCachedArgs p) 
             *reinterpret_cast<f32x4*>(orow + dd) = v;
           }
         }
+      if (p.lse && hh == 0) p.lse[((int64_t)c * p.H + h) * Kq + j] = m * 0.6931471805599453f + __logf(l);
+    }
+  }
+}
+
+// ------------------------------------------------------------------------------------------
+// Backward of the cached attention (request-grouped training).  A candidate's softmax row runs over the
+// request's Ic cached keys and its own n rows; with the row statistics of the whole row (lse, delta) the
+// two key ranges are independent sums, so the backward is three passes over disjoint outputs:
+//   own rows     attn_bwd_kernel on the candidate's n rows (I = n, K = Kq) with the whole-row lse / delta:
+//                dq (own-key part, stored), dk | dv of the n rows.  One wave owns a (candidate, head).
+//   cache dK/dV  attn_bwd_cached_kernel<HD, false>: one wave per (request, head, cached key block).  The
+//                request's candidates' kept queries are stacked (t = (c - c0) Kq + j) into 32-row query
+//                blocks, so c skinny attentions are one dense [c Kq] x Ic problem; the wave walks the
+//                stacked blocks in order and is the only writer of its 32 dK / dV rows.
+//   cache dQ     attn_bwd_cached_kernel<HD, true>: one workgroup per (request, head), a wave per stacked
+//                query block, walking the cached key blocks with P recomputed; the sum is added to the
+//                own-rows pass's dq (same stream, one writer per element).
+// No atomics, fixed summation order: bit-identical from run to run.  Every cached key is visible, so there
+// is no causal select here; padded keys (>= Ic) and padded stacked queries (lse = +inf) give P = 0.
+struct AttnCachedBwdArgs {
+  const float* qkv; int64_t ld;            // N-side rows [C*n, ld]
+  const float* kc; const float* vc; int64_t ldc;
+  const int32_t* req_start;                // [R+1]
+  const float* dout;                       // [C*Kq, d]
+  const float* stat;                       // attn_bwd_prep_kernel's lse | delta, [C*H][KP] each
+  float* dqkv; float* dkc; float* dvc;
+  int R, C, H, Ic, n, Kq, d, accumulate;
+  float scale;
+};
+
+template <int HD, bool DQ>
+__global__ __launch_bounds__(64 * BWD_WAVES<HD>(), HD >= 128 ? 1 : 2)   // hd 128 needs the whole register file
+void attn_bwd_cached_kernel(AttnCachedBwdArgs p) {
+  constexpr int LD = TLD<HD>();
+  constexpr int SLD = 36;
+  constexpr int NW = BWD_WAVES<HD>();
+  // per wave: the dK/dV pass holds the dO and Q blocks, the dQ pass the K block and the dS tile
+  constexpr int PER_WAVE = (DQ ? 32 * LD + 32 * SLD : 2 * 32 * LD) + 64;
+  __shared__ __attribute__((aligned(16))) float lds[NW * PER_WAVE];
+  const int lane = threadIdx.x & 63, li = lane & 31, hh = lane >> 5;
+  const int wave = threadIdx.x >> 6;
+  float* tO = lds + wave * PER_WAVE;                 // dO block   [query][dim]   (dK/dV pass)
+  float* tQ = tO + 32 * LD;                          // Q block    [query][dim]   (dK/dV pass)
+  float* tK = tO;                                    // K block    [key][dim]     (dQ pass)
+  float* tS = tK + 32 * LD;                          // dS block   [query][key]   (dQ pass)
+  float* rl = lds + wave * PER_WAVE + PER_WAVE - 64; // lse[32] | delta[32] of the query block
+  const int Ic = p.Ic, n = p.n, Kq = p.Kq, KP = attn_kpad(Kq);
+  const int nkb = (Ic + 31) / 32;
+  int r, h, kb_own = 0;
+  if constexpr (DQ) {
+    r = blockIdx.x / p.H; h = blockIdx.x % p.H;
+  } else {
+    const int64_t unit = (int64_t)blockIdx.x * NW + wave;
+    if (unit >= (int64_t)p.R * p.H * nkb) return;
+    kb_own = (int)(unit % nkb);
+    const int rh = (int)(unit / nkb);
+    r = rh / p.H; h = rh % p.H;
+  }
+  int c0 = p.req_start[r], c1 = p.req_start[r + 1];
+  c0 = min(max(c0, 0), p.C); c1 = min(max(c1, c0), p.C);     // a bad map must not index out of the arrays
+  const int Qtot = (c1 - c0) * Kq, nqb = (Qtot + 31) / 32;
+  const float* Nq = p.qkv + h * HD;
+  const float* dO = p.dout + (int64_t)c0 * Kq * p.d + h * HD;
+  const float* Ck = p.kc + (int64_t)r * Ic * p.ldc + h * HD;
+  const float* Cv = p.vc + (int64_t)r * Ic * p.ldc + h * HD;
+  const float* dlt = p.stat + (int64_t)p.C * p.H * KP;
+
+  float qf[HD / 2], of[HD / 2], kf[HD / 2], vf[HD / 2];
+  int64_t qrow = 0;                                    // this lane's query row in [C*n]
+  bool qvalid = false;
+  // lane li: stacked query 32 qb + li (clamped to the last one; lse = +inf removes the padding)
+  auto load_qblock = [&](int qb) {
+    const int t = 32 * qb + li;
+    qvalid = t < Qtot;
+    const int tt = qvalid ? t : Qtot - 1;
+    const int cand = c0 + tt / Kq, j = tt % Kq;
+    qrow = (int64_t)cand * n + (n - Kq + j);
+    load_row_frag<HD>(qf, Nq + qrow * p.ld, hh);
+    load_row_frag<HD>(of, dO + (int64_t)tt * p.d, hh);
+    const int64_t si = ((int64_t)cand * p.H + h) * KP + j;
+    __builtin_amdgcn_wave_barrier();
+    if (hh == 0) rl[li] = qvalid ? p.stat[si] : INFINITY;
+    else rl[32 + li] = qvalid ? dlt[si] : 0.f;
+    if constexpr (!DQ) {
+      frag_to_lds<HD>(tO, of, li, hh);
+      frag_to_lds<HD>(tQ, qf, li, hh);
+    }
+    __builtin_amdgcn_wave_barrier();
+  };
+  // lane li: cached key 32 kb + li (zeros past Ic)
+  auto load_kblock = [&](int kb) {
+    const int key = 32 * kb + li;
+    load_row_frag<HD>(kf, key < Ic ? Ck + (int64_t)key * p.ldc : nullptr, hh);
+    load_row_frag<HD>(vf, key < Ic ? Cv + (int64_t)key * p.ldc : nullptr, hh);
+    if constexpr (DQ) {
+      __builtin_amdgcn_wave_barrier();
+      frag_to_lds<HD>(tK, kf, li, hh);
+      __builtin_amdgcn_wave_barrier();
+    }
+  };
+  // P (into s) and dS pre-scaled by 1/sqrt(hd) (into dp) of the loaded (query block, key block) pair
+  auto softmax_grad = [&](f32x16& s, f32x16& dp, int kb) {
+    s = mm_frag<HD>(qf, kf);                           // S: row = query, col = key
+    dp = mm_frag<HD>(of, vf);                          // dP: row = query, col = key
+    const bool kvalid = 32 * kb + li < Ic;
+#pragma unroll
+    for (int g = 0; g < 4; ++g) {
+      const f32x4 l4 = *reinterpret_cast<const f32x4*>(rl + 8 * g + 4 * hh);
+      const f32x4 d4 = *reinterpret_cast<const f32x4*>(rl + 32 + 8 * g + 4 * hh);
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        const int rr = 4 * g + e;
+        const float ex = __expf(s[rr] * p.scale - l4[e]);
+        const float P = kvalid ? ex : 0.f;
+        s[rr] = P;
+        dp[rr] = P * (dp[rr] - d4[e]) * p.scale;
+      }
+    }
+  };
+
+  if constexpr (!DQ) {
+    const int kpos = 32 * kb_own + li;
+    load_kblock(kb_own);
+    f32x16 dk[NB(HD)], dv[NB(HD)];
+#pragma unroll
+    for (int c = 0; c < NB(HD); ++c)
+#pragma unroll
+      for (int rr = 0; rr < 16; ++rr) { dk[c][rr] = 0.f; dv[c][rr] = 0.f; }
+    for (int qb = 0; qb < nqb; ++qb) {
+      load_qblock(qb);
+      f32x16 s, dp;
+      softmax_grad(s, dp, kb_own);
+      acc_tile_p<HD>(dv, tO, s, li, hh);               // dV^T += dO^T P
+      acc_tile_p<HD>(dk, tQ, dp, li, hh);              // dK^T += Q^T dS
+    }
+    if (kpos < Ic) {
+      float* dKr = p.dkc + ((int64_t)r * Ic + kpos) * p.ldc + h * HD;
+      float* dVr = p.dvc + ((int64_t)r * Ic + kpos) * p.ldc + h * HD;
+#pragma unroll
+      for (int c = 0; c < NB(HD); ++c)
+#pragma unroll
+        for (int g = 0; g < 4; ++g) {
+          const int dd = 32 * c + 8 * g + 4 * hh;
+          if (dd < HD) {
+            f32x4 a = {dk[c][4 * g], dk[c][4 * g + 1], dk[c][4 * g + 2], dk[c][4 * g + 3]};
+            f32x4 v = {dv[c][4 * g], dv[c][4 * g + 1], dv[c][4 * g + 2], dv[c][4 * g + 3]};
+            if (p.accumulate) {
+              a = *reinterpret_cast<const f32x4*>(dKr + dd) + a;
+              v = *reinterpret_cast<const f32x4*>(dVr + dd) + v;
+            }
+            *reinterpret_cast<f32x4*>(dKr + dd) = a;
+            *reinterpret_cast<f32x4*>(dVr + dd) = v;
+          }
+        }
+    }
+  } else {
+    for (int qb = wave; qb < nqb; qb += NW) {
+      load_qblock(qb);
+      f32x16 dq[NB(HD)];                               // dQ^T: lane = query, register = dim
+#pragma unroll
+      for (int c = 0; c < NB(HD); ++c)
+#pragma unroll
+        for (int rr = 0; rr < 16; ++rr) dq[c][rr] = 0.f;
+      for (int kb = 0; kb < nkb; ++kb) {
+        load_kblock(kb);
+        f32x16 s, dp;
+        softmax_grad(s, dp, kb);
+#pragma unroll
+        for (int g = 0; g < 4; ++g)
+#pragma unroll
+          for (int e = 0; e < 4; ++e) tS[(8 * g + 4 * hh + e) * SLD + li] = dp[4 * g + e];
+        __builtin_amdgcn_wave_barrier();
+        // dQ^T[d][q] += sum_key K[key][d] dS[q][key]
+#pragma unroll
+        for (int q4 = 0; q4 < 4; ++q4) {
+          const f32x4 a4 = *reinterpret_cast<const f32x4*>(tS + li * SLD + 16 * hh + 4 * q4);
+#pragma unroll
+          for (int e = 0; e < 4; ++e) {
+            const int key = 16 * hh + 4 * q4 + e;
+#pragma unroll
+            for (int c = 0; c < NB(HD); ++c) {
+              const int dd = 32 * c + li;
+              const float bkv = dd < HD ? tK[key * LD + dd] : 0.f;
+              dq[c] = __builtin_amdgcn_mfma_f32_32x32x2f32(bkv, a4[e], dq[c], 0, 0, 0);
+            }
+          }
+        }
+      }
+      if (qvalid) {                                    // added to the own-rows pass's dq
+        float* dqrow = p.dqkv + qrow * p.ld + h * HD + 4 * hh;
+#pragma unroll
+        for (int c = 0; c < NB(HD); ++c)
+#pragma unroll
+          for (int g = 0; g < 4; ++g) {
+            const int dd = 32 * c + 8 * g;
+            if (dd >= HD) continue;
+            const f32x4 v = {dq[c][4 * g], dq[c][4 * g + 1], dq[c][4 * g + 2], dq[c][4 * g + 3]};
+            *reinterpret_cast<f32x4*>(dqrow + dd) = *reinterpret_cast<const f32x4*>(dqrow + dd) + v;
+          }
+      }
     }
   }
 }
@@ -1844,6 +2047,95 @@ extern "C" int ot_attn_fwd_cached(const float* qkv, int64_t ld, const float* kv_
   const unsigned grid = ceil_div((int64_t)C * H, 4);
   OT_ATTN_DISPATCH(attn_fwd_cached_kernel, head_dim, dim3(grid), dim3(256), 0, (hipStream_t)stream, p);
   OT_LAUNCH_CHECK("ot_attn_fwd_cached");
+  return OT_OK;
+}
+
+extern "C" int ot_attn_fwd_cached_lse(const float* qkv, int64_t ld, const float* kv_cache, int64_t ldc,
+                                      const int32_t* req, int C, int H, int Ic, int n, int Kq, int head_dim,
+                                      float* out, float* lse, void* stream) {
+  OT_REQUIRE(C >= 0 && H > 0 && Ic >= 0 && n > 0 && Kq > 0 && Kq <= n,
+             "ot_attn_fwd_cached_lse: bad sizes C=%d Ic=%d n=%d Kq=%d", C, Ic, n, Kq);
+  const int d = H * head_dim;
+  OT_REQUIRE(ld % 4 == 0 && ld >= 3 * d && (Ic == 0 || (ldc % 4 == 0 && ldc >= 2 * d)),
+             "ot_attn_fwd_cached_lse: ld/ldc must hold k|v and be multiples of 4");
+  OT_REQUIRE(qkv && out && lse && req && (Ic == 0 || kv_cache), "ot_attn_fwd_cached_lse: null operand");
+  if (C == 0) return OT_OK;
+  AttnCachedArgs p{qkv, ld, kv_cache, kv_cache ? kv_cache + d : nullptr, ldc, req, out, C, H, Ic, n, Kq, d,
+                   1.f / sqrtf((float)head_dim), lse};
+  const unsigned grid = ceil_div((int64_t)C * H, 4);
+  OT_ATTN_DISPATCH(attn_fwd_cached_kernel, head_dim, dim3(grid), dim3(256), 0, (hipStream_t)stream, p);
+  OT_LAUNCH_CHECK("ot_attn_fwd_cached_lse");
+  return OT_OK;
+}
+
+extern "C" size_t ot_attn_bwd_workspace_size(int B, int H, int K);
+
+extern "C" size_t ot_attn_bwd_cached_workspace_size(int R, int C, int H, int Ic, int n, int Kq, int head_dim) {
+  (void)R; (void)Ic; (void)n; (void)head_dim;
+  if (C <= 0 || H <= 0 || Kq <= 0) return 0;
+  return ot_attn_bwd_workspace_size(C, H, Kq);                 // padded lse | delta of every (candidate, head)
+}
+
+template <int HD>
+static void attn_bwd_cached_launch(const AttnCachedBwdArgs& p, hipStream_t stream) {
+  constexpr int NW = BWD_WAVES<HD>();
+  const int nkb = (p.Ic + 31) / 32;
+  hipLaunchKernelGGL((attn_bwd_cached_kernel<HD, false>), dim3((unsigned)ceil_div((int64_t)p.R * p.H * nkb, NW)),
+                     dim3(64 * NW), 0, stream, p);
+  if (p.C > 0)
+    hipLaunchKernelGGL((attn_bwd_cached_kernel<HD, true>), dim3((unsigned)((int64_t)p.R * p.H)), dim3(64 * NW), 0,
+                       stream, p);
+}
+
+extern "C" int ot_attn_bwd_cached(const float* qkv, int64_t ld, const float* kv_cache, int64_t ldc,
+                                  const int32_t* req_start, int R, int C, int H, int Ic, int n, int Kq,
+                                  int head_dim, const float* out, const float* dout, const float* lse, float* dqkv,
+                                  float* dkv_cache, int accumulate, void* workspace, size_t ws_bytes, void* stream) {
+  OT_REQUIRE(R >= 0 && C >= 0 && H > 0 && Ic >= 0 && n > 0 && Kq > 0 && Kq <= n,
+             "ot_attn_bwd_cached: bad sizes R=%d C=%d Ic=%d n=%d Kq=%d", R, C, Ic, n, Kq);
+  OT_REQUIRE(head_dim == 16 || head_dim == 32 || head_dim == 64 || head_dim == 128,
+             "ot_attn_bwd_cached: head_dim %d unsupported", head_dim);
+  OT_REQUIRE((int64_t)R * H * ((Ic + 31) / 32) < (int64_t)1 << 31 && (int64_t)C * H < (int64_t)1 << 31,
+             "ot_attn_bwd_cached: grid too large");
+  const int d = H * head_dim;
+  OT_REQUIRE(ld % 4 == 0 && ld >= 3 * d && (Ic == 0 || (ldc % 4 == 0 && ldc >= 2 * d)),
+             "ot_attn_bwd_cached: ld/ldc must hold k|v and be multiples of 4");
+  OT_REQUIRE(accumulate == 0 || accumulate == 1, "ot_attn_bwd_cached: accumulate is 0 or 1");
+  const size_t need = ot_attn_bwd_cached_workspace_size(R, C, H, Ic, n, Kq, head_dim);
+  OT_REQUIRE(ws_bytes >= need, "ot_attn_bwd_cached: workspace too small (%zu < %zu)", ws_bytes, need);
+  OT_REQUIRE(qkv && out && dout && lse && dqkv && req_start && (Ic == 0 || (kv_cache && dkv_cache)) &&
+                 (need == 0 || workspace), "ot_attn_bwd_cached: null operand");
+  hipStream_t st = (hipStream_t)stream;
+  const float scale = 1.f / sqrtf((float)head_dim);
+  if (C > 0) {
+    // row statistics of the whole softmax row, then the candidate's own n rows: dq (stored), dk | dv
+    float* ws = (float*)workspace;
+    const int main_blocks = (int)ceil_div((int64_t)C * Kq * d / 4, 256);
+    const int pad_blocks = (int)ceil_div((int64_t)C * H * (attn_kpad(Kq) - Kq), 256);
+    hipLaunchKernelGGL(attn_bwd_prep_kernel, dim3(main_blocks + pad_blocks), dim3(256), 0, st, out, dout, lse, ws, C, H,
+                       Kq, head_dim, main_blocks, pad_blocks, (const int32_t*)nullptr);
+    OT_LAUNCH_CHECK("ot_attn_bwd_cached(prep)");
+    AttnArgs a{qkv, ld, d, out, dout, nullptr, const_cast<float*>(lse), dqkv, ws, C, H, n, Kq, scale, nullptr};
+    if (head_dim == 64) {
+      hipLaunchKernelGGL((attn_bwd_kernel<32, false, 2>), dim3((unsigned)((int64_t)C * H)), dim3(128), 0, st, a);
+    } else {
+      const int waves = head_dim >= 128 ? 2 : 4;
+      void (*kern)(AttnArgs) = head_dim == 16 ? attn_bwd_kernel<16, false>
+                               : head_dim == 32 ? attn_bwd_kernel<32, false> : attn_bwd_kernel<128, false>;
+      hipLaunchKernelGGL(kern, dim3((unsigned)ceil_div((int64_t)C * H, waves)), dim3(64 * waves), 0, st, a);
+    }
+    OT_LAUNCH_CHECK("ot_attn_bwd_cached(own rows)");
+  }
+  if (Ic == 0 || R == 0) return OT_OK;
+  AttnCachedBwdArgs p{qkv, ld, kv_cache, kv_cache + d, ldc, req_start, dout, (const float*)workspace, dqkv,
+                      dkv_cache, dkv_cache + d, R, C, H, Ic, n, Kq, d, accumulate, scale};
+  switch (head_dim) {
+    case 16: attn_bwd_cached_launch<16>(p, st); break;
+    case 32: attn_bwd_cached_launch<32>(p, st); break;
+    case 64: attn_bwd_cached_launch<64>(p, st); break;
+    default: attn_bwd_cached_launch<128>(p, st); break;
+  }
+  OT_LAUNCH_CHECK("ot_attn_bwd_cached");
   return OT_OK;
 }
 

@@ -146,3 +146,31 @@ def make_batch(batch_size: int, config: OneTransConfig, seed: int = 1000,
     if config.sparse_features or config.seq_item_vocab:
         return criteo_batch(batch_size, config, seq_lens, seed, teacher)
     return create_sample_batch(batch_size, config, seq_lens, seed)
+
+
+RequestBatch = Tuple[Dict[str, np.ndarray], Dict[str, np.ndarray], Dict[str, np.ndarray], np.ndarray]
+
+
+def make_request_batch(R: int, cands, config: OneTransConfig, seed: int = 1000,
+                       seq_lens: Optional[List[int]] = None, teacher: str = 'ids') -> RequestBatch:
+    """A request-grouped batch ``(non_seq, seq, labels, req)``: R requests' sequences (and, for
+    ``seq_fusion='time'``, their ``*_time`` arrays) with R rows, C candidates' non-sequence features and labels
+    with C rows, and ``req`` int32 [C], non-decreasing: the request of each candidate.  ``cands``: candidates
+    per request, an int or a list of R counts (zeros allowed).  The candidate side is ``make_batch(C, seed)``'s,
+    the request side ``make_batch(R, seed + 1)``'s sequences."""
+    counts = [int(cands)] * R if np.isscalar(cands) else [int(c) for c in cands]
+    if len(counts) != R or any(c < 0 for c in counts):
+        raise ValueError(f'cands: {R} non-negative counts expected, got {counts}')
+    C = sum(counts)
+    ns, _, labels = make_batch(C, config, seed, seq_lens, teacher)
+    _, seq, _ = make_batch(R, config, seed + 1, seq_lens, teacher)
+    req = np.repeat(np.arange(R, dtype=np.int32), counts)
+    return ns, seq, labels, req
+
+
+def expand_requests(batch: RequestBatch) -> Batch:
+    """The per-sample 3-tuple equal to a request-grouped batch: every sequence array (``*_time`` included)
+    gathered by ``req``, so candidate c carries a copy of its request's sequences."""
+    ns, seq, labels, req = batch
+    idx = np.asarray(req, dtype=np.int64)
+    return ns, {k: np.asarray(v)[idx] for k, v in seq.items()}, labels

@@ -454,6 +454,30 @@ def attn_fwd_cached(qkv, ld, kv_cache, ldc, req, C, H, Ic, n, Kq, hd, out) -> No
                    f'fwd_cached Ic{Ic} n{n} K{Kq} hd{hd}')
 
 
+def attn_fwd_cached_lse(qkv, ld, kv_cache, ldc, req, C, H, Ic, n, Kq, hd, out, lse) -> None:
+    """ot_attn_fwd_cached_lse: attn_fwd_cached that also writes lse [C, H, Kq] for the backward."""
+    ev = _probe.begin() if _probe is not None else None
+    call('ot_attn_fwd_cached_lse', ptr(qkv), ld, ptr(kv_cache), ldc, ptr(req), C, H, Ic, n, Kq, hd, ptr(out),
+         ptr(lse), stream())
+    if ev is not None:
+        _probe.end('attention', 4.0 * (Kq * (Ic + n) - Kq * (Kq - 1) / 2) * hd * H * C, ev,
+                   f'fwd_cached_lse Ic{Ic} n{n} K{Kq} hd{hd}')
+
+
+def attn_bwd_cached(qkv, ld, kv_cache, ldc, req_start, R, C, H, Ic, n, Kq, hd, out, dout, lse, dqkv, dkv_cache,
+                    accumulate: bool = False) -> None:
+    """ot_attn_bwd_cached: dq / dk / dv of the candidates' rows into dqkv, the cached rows' dK / dV (summed over a
+    request's candidates, deterministic) into dkv_cache (written, or added to with ``accumulate``)."""
+    ws = workspace(size('ot_attn_bwd_cached_workspace_size', R, C, H, Ic, n, Kq, hd), qkv.device)
+    ev = _probe.begin() if _probe is not None else None
+    call('ot_attn_bwd_cached', ptr(qkv), ld, ptr(kv_cache), ldc, ptr(req_start), R, C, H, Ic, n, Kq, hd, ptr(out),
+         ptr(dout), ptr(lse), ptr(dqkv), ptr(dkv_cache), int(bool(accumulate)), ptr(ws), ws.numel(), stream())
+    if ev is not None:
+        # own rows once; the cached part's S / dP are formed twice (dK/dV pass and the recomputing dQ pass)
+        _probe.end('attention', (8.0 * (Kq * n - Kq * (Kq - 1) / 2) + 14.0 * Kq * Ic) * hd * H * C, ev,
+                   f'bwd_cached Ic{Ic} n{n} K{Kq} hd{hd}')
+
+
 def rmsnorm_fwd(x: Ptrish, ldx: int, rows: int, d: int, rstd: Ptrish, gamma: Ptrish = None, y: Ptrish = None,
                 ldy: int = 0, eps: float = 1e-6) -> None:
     ev = _probe.begin() if _probe is not None else None

@@ -1276,6 +1276,23 @@ class OneTransModel(nn.Module):
         probs._ot_logits = logits            # keras_bce_loss takes the BCE from the logits (Keras _keras_logits)
         return probs
 
+    # ---------------------------------------------------------------- request-grouped forward
+    def forward_requests(self, non_seq_features, seq_features, req, training: bool = False, validate: bool = True):
+        """Request-grouped forward (paper §3.5.1 in training; recommend_amd/request_train.py): ``seq_features``
+        hold R rows (one per request), ``non_seq_features`` C rows (one per candidate), ``req`` [C] integers,
+        non-decreasing, in [0, R): the request of each candidate.  The S side of every layer runs once per
+        request.  Returns {task: probs [C, 1]}, equal to ``forward`` on the expanded batch (each candidate with
+        a copy of its request's sequences).  ``validate`` checks ``req`` with one small read-back before any
+        launch (ValueError); with False the caller vouches for it."""
+        probs = self.forward_probs_requests(non_seq_features, seq_features, req, bool(training), validate)
+        return {t: probs[i].view(-1, 1) for i, t in enumerate(self.config.tasks)}
+
+    @in_model_precision
+    def forward_probs_requests(self, ns, seq, req, training: bool = False, validate: bool = True) -> torch.Tensor:
+        """All tasks as one [T, C] tensor (``_ot_logits`` set, like ``forward_probs``)."""
+        from . import request_train
+        return request_train.forward_probs_requests(self, ns, seq, req, training, validate)
+
     def route_ahead(self, seq_features: Dict) -> None:
         """Look-ahead routing of the row-sharded item table (sharded.py ShardedTable.route): issue the routing of
         the NEXT forward's sequence ids now — the trainer calls it between step i's forward and backward with

@@ -42,6 +42,21 @@ from .layout import layer_maps
 RMS_EPS = 1e-6
 
 
+def request_schedule(cfg, L_S: int) -> List[Dict]:
+    """The two-stage split of every layer (serving and request-grouped training): S rows s, N rows n, kept S
+    rows kS, kept N rows kN (kS + kN = the layer's keep; the tail keep takes the N rows first)."""
+    L_NS = cfg.num_ns_tokens
+    sched = cfg.pyramid_schedule(L_S + L_NS)
+    out, s, n = [], L_S, L_NS
+    for l, e in enumerate(sched):
+        keep = e['keep'] if l < len(sched) - 1 else 1        # only the last token is read (model.py:390)
+        kN = min(keep, n)
+        kS = keep - kN
+        out.append({'I': s + n, 's': s, 'n': n, 'kS': kS, 'kN': kN})
+        s, n = kS, kN
+    return out
+
+
 class RequestCache:
     """Stage-I output for R requests: per layer the S-side qkv rows [R*Ic, 3d] (k at col d, v at 2d)
     and Ic, the number of S tokens in that layer's input."""
@@ -73,17 +88,7 @@ class OneTransServer:
         return self.m
     def schedule(self, L_S: int) -> List[Dict]:
         """Per layer: S rows s, N rows n, kept S rows kS, kept N rows kN (kS + kN = the layer's keep)."""
-        cfg = self.m.config
-        L_NS = cfg.num_ns_tokens
-        sched = cfg.pyramid_schedule(L_S + L_NS)
-        out, s, n = [], L_S, L_NS
-        for l, e in enumerate(sched):
-            keep = e['keep'] if l < len(sched) - 1 else 1        # only the last token is read (model.py:390)
-            kN = min(keep, n)
-            kS = keep - kN
-            out.append({'I': s + n, 's': s, 'n': n, 'kS': kS, 'kN': kN})
-            s, n = kS, kN
-        return out
+        return request_schedule(self.m.config, L_S)
 
     def _layer_maps(self, B, I, Kq, p0, I_full):
         key = (B, I, Kq, p0, I_full)

@@ -46,6 +46,15 @@ def _seq_inputs(model, seq: Dict, dev) -> Dict:
     return dict(seq)
 
 
+def _split_batch(batch_data):
+    """(non_seq, seq, labels, req): a 3-tuple batch has req None; a 4-tuple is request-grouped
+    (data.make_request_batch: sequences per request, ``req`` [C] the request of each candidate)."""
+    if len(batch_data) == 4:
+        return batch_data
+    non_seq, seq, labels = batch_data
+    return non_seq, seq, labels, None
+
+
 def label_rank(labels) -> int:
     """Rank of the caller's per-task labels: 1 for [B] (get_tf_dataset's batched scalars), 2 for [B, 1]
     (create_sample_batch) and for an already stacked [T, B] tensor.  It picks the BCE form (keras_bce_loss)."""
@@ -412,11 +421,15 @@ class OneTransTrainer:
         """train.py:111-155.  Returns {'total_loss': device scalar} (no host sync).  ``next_batch`` (optional, the
         batch the next call will get, e.g. from a prefetching loader): a row-sharded table routes its ids during
         this step (OneTransModel.route_ahead)."""
-        non_seq, seq, labels = batch_data
+        non_seq, seq, labels, req = _split_batch(batch_data)
         dev = self.device
         y = labels if isinstance(labels, torch.Tensor) else stack_labels(labels, self.config.tasks, dev)
         self.model.train()
-        probs = self.model.forward_probs(_to_dev(non_seq, dev), _seq_inputs(self.model, seq, dev), training=True)
+        if req is not None:      # request-grouped: seq holds one row per request, req the request of each candidate
+            probs = self.model.forward_probs_requests(_to_dev(non_seq, dev), _seq_inputs(self.model, seq, dev), req,
+                                                      training=True)
+        else:
+            probs = self.model.forward_probs(_to_dev(non_seq, dev), _seq_inputs(self.model, seq, dev), training=True)
         if next_batch is not None and self.model.sharded:
             self.model.route_ahead(_seq_inputs(self.model, next_batch[1], dev))
         loss = keras_bce_loss(y, probs, self.config.tasks, label_rank(labels))
@@ -433,10 +446,14 @@ class OneTransTrainer:
     @torch.no_grad()
     def val_step(self, batch_data) -> Dict[str, torch.Tensor]:
         """train.py:158-190."""
-        non_seq, seq, labels = batch_data
+        non_seq, seq, labels, req = _split_batch(batch_data)
         dev = self.device
         y = labels if isinstance(labels, torch.Tensor) else stack_labels(labels, self.config.tasks, dev)
-        probs = self.model.forward_probs(_to_dev(non_seq, dev), _seq_inputs(self.model, seq, dev), training=False)
+        if req is not None:
+            probs = self.model.forward_probs_requests(_to_dev(non_seq, dev), _seq_inputs(self.model, seq, dev), req,
+                                                      training=False)
+        else:
+            probs = self.model.forward_probs(_to_dev(non_seq, dev), _seq_inputs(self.model, seq, dev), training=False)
         loss = keras_bce_loss(y, probs, self.config.tasks, label_rank(labels))
         if self.val_metrics is not None:                 # train.py:176-185
             self.val_metrics.update(y, probs)

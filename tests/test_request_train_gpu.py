@@ -1,0 +1,306 @@
+"""GPU: request-grouped training (recommend_amd/request_train.py) against the existing model on the expanded
+batch (data.expand_requests: every candidate paired with a copy of its request's sequences) and against the
+float64 oracle on that batch.
+
+Bounds (as tests/test_model_gpu.py): probabilities 1e-4 absolute, gradients 2e-4 relative to the
+gradient's largest element, against the oracle; twice that between the two GPU paths (each is within one
+bound of the oracle)."""
+
+import numpy as np
+import pytest
+import torch
+
+pytestmark = pytest.mark.gpu
+
+from recommend_amd.config import workload_config
+from recommend_amd.data import expand_requests, make_request_batch
+from recommend_amd.model import OneTransModel, keras_bce_loss
+from recommend_amd.params import init_params
+from recommend_amd.request_train import n_span_seed
+from recommend_amd.serving import request_schedule
+from recommend_amd.trainer import OneTransTrainer, stack_labels
+from oracle import keras_math as km
+from oracle import onetrans_ref as R
+
+import time_fusion_ref as TF
+
+PROB_TOL, GRAD_TOL = 1e-4, 2e-4
+CANDS = [3, 0, 4]
+
+
+def small(d=64, H=2, fusion='sep', rate=0.0):
+    cfg = workload_config('C2')
+    cfg.hidden_dim, cfg.num_heads, cfg.ffn_dim, cfg.num_layers, cfg.num_ns_tokens = d, H, 2 * d, 3, 4
+    cfg.sparse_features = {k: 40 + 7 * i for i, k in enumerate(cfg.sparse_features)}
+    cfg.seq_item_vocab = 300
+    cfg.feature_config = dict(cfg.feature_config,
+                              sequence_features=list(cfg.feature_config['sequence_features'][:2]))
+    cfg._seq_lens = [5, 7]
+    cfg.dedicated_positions = 'tail'
+    cfg.pyramid_enabled = True
+    cfg.pyramid_ratios = [0.5, 0.25, 0.2]
+    cfg.seq_fusion = fusion
+    cfg.dropout_rate = rate
+    return cfg
+
+
+def t_(d, dev):
+    return {k: torch.from_numpy(np.ascontiguousarray(v)).to(dev) for k, v in d.items()}
+
+
+def test_schedule_has_the_shapes_this_file_is_about():
+    for fusion in ('sep', 'time'):
+        cfg = small(fusion=fusion)
+        L_S = 12 if fusion == 'time' else 13
+        sch = request_schedule(cfg, L_S)
+        assert [e['s'] > 0 for e in sch] == [True, True, False]
+        assert sch[0]['kS'] > 0 and sch[1]['kS'] == 0 and sch[2]['kS'] == 0 and sch[2]['kN'] == 1
+
+
+def grads_of(model):
+    out = {}
+    for name in model.layout.shapes:
+        out[name] = model.g(name).double().cpu().clone()
+    sparse = {}
+    for (tname, keys, grads) in model._pending_sparse:
+        dense = torch.zeros(model.tables[tname].shape, dtype=torch.float64)
+        dense.index_add_(0, keys.cpu(), grads.double().cpu())
+        sparse[tname] = dense
+    return out, sparse
+
+
+def run_requests(model, cfg, batch, dev, training):
+    ns, seq, lab, req = batch
+    model.flat.grad.fill_(float('nan'))
+    probs = model.forward_probs_requests(t_(ns, dev), t_(seq, dev), torch.from_numpy(req).to(dev), training=training)
+    loss = keras_bce_loss(stack_labels(lab, cfg.tasks, dev), probs, cfg.tasks)
+    loss.backward()
+    g, sp = grads_of(model)
+    return probs.detach().double().cpu(), loss.item(), g, sp
+
+
+def run_expanded(model, cfg, batch, dev):
+    ns, seq, lab = expand_requests(batch)
+    model.flat.grad.fill_(float('nan'))
+    probs = model.forward_probs(t_(ns, dev), t_(seq, dev), training=False)
+    loss = keras_bce_loss(stack_labels(lab, cfg.tasks, dev), probs, cfg.tasks)
+    loss.backward()
+    g, sp = grads_of(model)
+    return probs.detach().double().cpu(), loss.item(), g, sp
+
+
+def close(got, want, tol, what):
+    assert not torch.isnan(got).any(), what
+    scale = max(1e-3, want.abs().max().item())
+    err = (got.reshape(want.shape) - want).abs().max().item() / scale
+    print(f'{what}: rel err {err:.2e} (bound {tol:.1e})')
+    assert err < tol, f'{what}: rel err {err:.2e}'
+
+
+def compare(a, b, mult, what, oracle_b=False):
+    """a = (probs, loss, grads, sparse) of the request path; b the same of the other side."""
+    pa, la, ga, sa = a
+    pb, lb, gb, sb = b
+    err = (pa - pb.reshape(pa.shape)).abs().max().item()
+    print(f'{what}: probs abs err {err:.2e}, loss {la:.6f} vs {lb:.6f}')
+    assert err < mult * PROB_TOL, f'{what}: probs {err:.2e}'
+    assert abs(la - lb) < mult * 1e-4
+    for name, g in ga.items():
+        r = gb[name]
+        if oracle_b and name == 'tok.ns.kernel':
+            assert torch.all(g[r.shape[0]:] == 0)
+            g = g[:r.shape[0]]
+        close(g, r, mult * GRAD_TOL, f'{what} {name}')
+    assert set(sa) == set(sb) == {'emb.ns', 'emb.seq_item'}
+    for name in sa:
+        close(sa[name], sb[name], mult * GRAD_TOL, f'{what} {name}')
+
+
+def oracle_side(P, cfg, batch, training=False, seed=0):
+    ns, seq, lab = expand_requests(batch)
+    rl, rg, rout = R.loss_and_grads(R.to_torch(P), cfg, R.to_torch(ns), R.to_torch(seq), R.to_torch(lab),
+                                    training=training, seed=seed)
+    probs = torch.stack([rout['probs'][t].detach().reshape(-1) for t in cfg.tasks])
+    dense = {k: v for k, v in rg.items() if not k.startswith('emb.')}
+    sparse = {k: v for k, v in rg.items() if k.startswith('emb.')}
+    return probs, rl.item(), dense, sparse
+
+
+def case(cfg, dev, cands=CANDS, R_=3):
+    P = init_params(cfg, cfg.ns_input_width(), seed=0, perturb=True)
+    model = OneTransModel(cfg, device=dev, init=P)
+    return P, model, make_request_batch(R_, cands, cfg, seed=1000)
+
+
+@pytest.mark.parametrize('d,H', [(64, 2), (128, 2)])
+def test_request_mode_matches_expanded_batch_and_oracle(dev, d, H):
+    cfg = small(d, H)
+    P, model, batch = case(cfg, dev)
+    before = model.forward_probs(*[t_(x, dev) for x in expand_requests(batch)[:2]], training=False).detach().clone()
+    got = run_requests(model, cfg, batch, dev, training=False)
+    compare(got, run_expanded(model, cfg, batch, dev), 2, 'vs expanded')
+    compare(got, oracle_side(P, cfg, batch), 1, 'vs oracle', oracle_b=True)
+    # regression guard: the default path after a request-mode step gives what it gave before it
+    after = model.forward_probs(*[t_(x, dev) for x in expand_requests(batch)[:2]], training=False).detach()
+    assert torch.equal(before, after)
+
+
+def test_request_mode_time_fusion(dev, monkeypatch):
+    monkeypatch.setattr(R, 'tokenizer', TF.tokenizer_time)          # the oracle's time-ordered tokenizer
+    cfg = small(fusion='time')
+    P, model, batch = case(cfg, dev)
+    got = run_requests(model, cfg, batch, dev, training=False)
+    compare(got, run_expanded(model, cfg, batch, dev), 2, 'time vs expanded')
+    compare(got, oracle_side(P, cfg, batch), 1, 'time vs oracle', oracle_b=True)
+
+
+def test_one_candidate_per_request(dev):
+    cfg = small()
+    P, model, batch = case(cfg, dev, cands=1, R_=5)
+    assert batch[3].tolist() == list(range(5))
+    got = run_requests(model, cfg, batch, dev, training=False)
+    compare(got, run_expanded(model, cfg, batch, dev), 2, 'c=1 vs expanded')
+    compare(got, oracle_side(P, cfg, batch), 1, 'c=1 vs oracle', oracle_b=True)
+
+
+def request_masks(cfg, L_S, req):
+    """oracle apply_dropout for the expanded batch with the request mode's masks: row (c, p) of a
+    layer with s S rows and n N rows hashes (req[c]*s + p)*d + col under the layer seed when p < s, and
+    (c*n + p - s)*d + col under the N span's seed otherwise."""
+    sched = request_schedule(cfg, L_S)
+    req = np.asarray(req).astype(np.int64)
+
+    def apply(y, training, rate, seed, site, I, positions):
+        if not training or rate <= 0.0:
+            return y
+        B, K_, d = y.shape
+        e = sched[site // 2]
+        s, n = e['s'], e['n']
+        assert I == s + n and B == len(req)
+        pos = np.asarray(positions).astype(np.int64)
+        assert pos.ndim == 1
+        col = np.arange(d, dtype=np.int64)[None, None, :]
+        is_s = pos < s
+        idx_s = (req[:, None, None] * s + np.where(is_s, pos, 0)[None, :, None]) * d + col
+        idx_n = (np.arange(B)[:, None, None] * n + np.where(is_s, 0, pos - s)[None, :, None]) * d + col
+        keep = np.where(is_s[None, :, None], km.dropout_keep(seed, site, idx_s.astype(np.uint64), rate),
+                        km.dropout_keep(n_span_seed(seed), site, idx_n.astype(np.uint64), rate))
+        return y * torch.from_numpy(keep.astype(np.float64) / (1.0 - rate)).to(y.dtype)
+
+    return apply
+
+
+def test_dropout_masks_follow_the_written_rule(dev, monkeypatch):
+    cfg = small(rate=0.1)
+    P, model, batch = case(cfg, dev)
+    step0 = model._step
+    a = run_requests(model, cfg, batch, dev, training=True)
+    seed = (model.dropout_seed + 0x9E3779B9 * model._step) & 0xFFFFFFFF
+    model._step = step0
+    b = run_requests(model, cfg, batch, dev, training=True)
+    assert torch.equal(a[0], b[0]) and a[1] == b[1]
+    for name in a[2]:
+        assert torch.equal(a[2][name], b[2][name]), name
+    for name in a[3]:
+        assert torch.equal(a[3][name], b[3][name]), name
+    monkeypatch.setattr(R, 'apply_dropout', request_masks(cfg, 13, batch[3]))
+    ref = oracle_side(P, cfg, batch, training=True, seed=seed)
+    off = oracle_side(P, cfg, batch, training=False)
+    assert abs(ref[1] - off[1]) > 1e-5                      # the masks do act on this batch
+    compare(a, ref, 1, 'dropout vs oracle', oracle_b=True)
+
+
+def test_trainer_steps_match_expanded(dev):
+    cfg = small()
+    cfg.optimizer_config = dict(cfg.optimizer_config, dense_lr=0.001, momentum=0.9)
+    P = init_params(cfg, cfg.ns_input_width(), seed=0, perturb=True)
+    trs = [OneTransTrainer(cfg, model=OneTransModel(cfg, device=dev, init=P)) for _ in range(2)]
+    for tr in trs:
+        tr.enable_metrics()
+    for step in range(3):
+        batch = make_request_batch(3, CANDS, cfg, seed=2000 + step)
+        la = trs[0].train_step(batch)['total_loss'].item()
+        lb = trs[1].train_step(expand_requests(batch))['total_loss'].item()
+        print(f'step {step}: loss {la:.6f} vs {lb:.6f}')
+        assert abs(la - lb) < 2e-4, step
+    pa, pb = trs[0].model.param_dict(), trs[1].model.param_dict()
+    for name in pb:
+        err = np.abs(pa[name] - pb[name]).max()
+        assert err < 2e-4, f'{name} after 3 steps: {err:.2e}'
+    ma, mb = (tr.metric_results(tr.train_metrics) for tr in trs)
+    assert set(ma) == set(mb)
+    for k in ma:
+        assert abs(ma[k] - mb[k]) < 1e-3, k
+
+
+def test_val_step_and_grouped_auc_on_request_batches(dev):
+    cfg = small()
+    P = init_params(cfg, cfg.ns_input_width(), seed=0, perturb=True)
+    sparse = [n for n in cfg.ns_feature_names() if n in cfg.sparse_features]
+    trs = [OneTransTrainer(cfg, model=OneTransModel(cfg, device=dev, init=P)) for _ in range(2)]
+    for tr in trs:
+        tr.enable_metrics(group_feature=sparse[0])
+    batch = make_request_batch(6, [3, 0, 4, 2, 5, 1], cfg, seed=77)
+    oa = trs[0].val_step(batch)
+    ob = trs[1].val_step(expand_requests(batch))
+    assert oa['probs'].shape == ob['probs'].shape == (len(cfg.tasks), 15)
+    assert (oa['probs'] - ob['probs']).abs().max().item() < 2 * PROB_TOL
+    assert abs(oa['total_loss'].item() - ob['total_loss'].item()) < 2e-4
+    ra, rb = (tr.metric_results(tr.val_metrics, extended=True) for tr in trs)
+    assert set(ra) == set(rb) and len(ra) > 0
+    for k in ra:
+        assert abs(ra[k] - rb[k]) < 1e-3, k
+    assert trs[0].val_grouped is not None
+    trs[0].train_step(batch)
+    trs[1].train_step(expand_requests(batch))
+    ta, tb = (tr.metric_results(tr.train_metrics, extended=True) for tr in trs)
+    for k in ta:
+        assert abs(ta[k] - tb[k]) < 1e-3, k
+
+
+def test_bad_req_is_refused_before_launch(dev):
+    cfg = small()
+    P, model, batch = case(cfg, dev)
+    ns, seq, lab, req = batch
+    nsd, sqd = t_(ns, dev), t_(seq, dev)
+    step0 = model._step
+    for bad, msg in (([0, 2, 0, 2, 2, 2, 2], 'non-decreasing'), ([0, 0, 0, 2, 2, 2, 3], 'out of range'),
+                     ([-1, 0, 0, 2, 2, 2, 2], 'out of range'), ([0, 0, 0, 2, 2, 2], 'expected'),
+                     ([0, 0, 0, 2, 2, 2, 2, 2], 'expected')):
+        with pytest.raises(ValueError, match=msg):
+            model.forward_probs_requests(nsd, sqd, torch.tensor(bad, dtype=torch.int32, device=dev), training=True)
+    with pytest.raises(ValueError):
+        model.forward_probs_requests(nsd, sqd, torch.tensor([0.0] * 7), training=True)
+    assert model._step == step0                              # nothing ran
+    out = model.forward_requests(nsd, sqd, req, validate=False)
+    assert set(out) == set(cfg.tasks) and all(v.shape == (7, 1) for v in out.values())
+
+
+def test_unsupported_modes_are_refused(dev):
+    def attempt(cfg, **attrs):
+        model = OneTransModel(cfg, device=dev)
+        for k, v in attrs.items():
+            setattr(model, k, v)
+        ns, seq, lab, req = make_request_batch(3, CANDS, cfg, seed=1)
+        model.forward_probs_requests(t_(ns, dev), t_(seq, dev), req)
+
+    cfg = small()
+    cfg.pyramid_select = 'norm'
+    with pytest.raises(ValueError, match='pyramid_select'):
+        attempt(cfg)
+    cfg = small()
+    cfg.compute_dtype = 'bf16'
+    with pytest.raises(NotImplementedError, match='bf16'):
+        attempt(cfg)
+    cfg = small(d=128, H=2)
+    cfg.compute_dtype = 'fp8attn'
+    with pytest.raises(NotImplementedError, match='fp8attn'):
+        attempt(cfg)
+    cfg = small()
+    cfg.recompute_blocks = True
+    with pytest.raises(NotImplementedError, match='recompute'):
+        attempt(cfg)
+    cfg = small()
+    cfg.table_sharding = 'row'
+    with pytest.raises(NotImplementedError, match='row-sharded'):
+        attempt(cfg)
