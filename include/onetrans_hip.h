@@ -740,6 +740,49 @@ size_t ot_seq_time_rows_workspace_size(int B, int nseq, int L_S);
 int ot_seq_time_rows(const ot_seq_time* seqs, int nseq, int B, int L_S, int64_t row_stride, int32_t* out_rows,
                      int32_t* rank_out, int64_t* last_time, void* workspace, size_t ws_bytes, void* stream);
 
+/* ---- embedding bags (bag.hip) -----------------------------------------------------------------
+ * Multi-valued NS id features pooled into one column block of the NS concat matrix each, and the
+ * (key, gradient row) pairs of their slots for ot_sparse_adagrad.  Stream-ordered, no allocation, no
+ * host sync, no atomics: results are bitwise reproducible.
+ *   bags      nbags HOST descriptors (1 .. OT_NS_BAG_MAX), read at call time and passed to the kernel by
+ *             value.  ids: device int64, sample b's cap slots at ids + b * ids_stride; a slot whose id is
+ *             outside [0, num_rows) is EMPTY: never read, coefficient 0, key -1.  weights: NULL, or device
+ *             f32 per slot at weights + b * weights_stride (pooling OT_BAG_SUM only).  table: device f32
+ *             rows of `width` floats, 16-byte aligned; the caller vouches that rows row_offset ..
+ *             row_offset + num_rows - 1 exist.  Strides are in elements, >= cap.
+ *   pool      out[b][col .. col + width) = sum over the valid slots of coef * table[row_offset + id],
+ *             coef = w_j * s_b, w_j = 1 without weights, s_b = 1 (SUM) or 1.0f / (valid slots of the
+ *             bag) (MEAN); an empty bag gives zeros.  Every other column of out is untouched.
+ *             coef_out[base_f + b * cap_f + j] = that coefficient (0 for an empty slot), base_f = B * (cap_0
+ *             + .. + cap_{f-1}) over the descriptors of THIS call: sum of B * cap floats.
+ *   grad_pack the bags of one table (equal width E; `table` is not read): for slot position p = base_f +
+ *             b * cap_f + j, keys[p] = row_offset + id or -1 (empty), grads[p][c] = coef[p] * dmat[b][col + c]
+ *             (one f32 multiply; zeros for an empty slot).  coef: the pool's coef_out, at the first
+ *             descriptor's base.  grads 16-byte aligned.
+ * width % 4 == 0 and width <= OT_NS_BAG_MAX_WIDTH, cap >= 1, col + width <= ld, B * cap < 2^31 in total;
+ * anything else, or a null operand, returns OT_ERR_INVALID_ARG without launching.  B = 0 is a no-op. */
+#define OT_NS_BAG_MAX 32
+#define OT_NS_BAG_MAX_WIDTH 256
+#define OT_BAG_SUM 0
+#define OT_BAG_MEAN 1
+typedef struct {
+  const float* table;     /* device, rows of `width` floats */
+  const int64_t* ids;     /* device, [B] rows of cap ids, row stride ids_stride */
+  const float* weights;   /* device, [B] rows of cap weights, row stride weights_stride, or NULL */
+  int64_t row_offset;     /* row of id 0 in the table */
+  int64_t num_rows;       /* ids outside [0, num_rows) are empty slots */
+  int64_t ids_stride;
+  int64_t weights_stride;
+  int32_t width;          /* E */
+  int32_t cap;            /* slots per sample */
+  int32_t col;            /* first destination column */
+  int32_t pooling;        /* OT_BAG_SUM | OT_BAG_MEAN */
+} ot_ns_bag;
+int ot_ns_bag_pool(const ot_ns_bag* bags, int nbags, int B, float* out, int64_t ld_out, float* coef_out,
+                   void* stream);
+int ot_ns_bag_grad_pack(const ot_ns_bag* bags, int nbags, int B, const float* dmat, int64_t ld, const float* coef,
+                        int64_t* keys, float* grads, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -56,6 +56,19 @@ class SeqTime(ctypes.Structure):
     _fields_ = [('times', c_void_p), ('stride_b', c_int64), ('L', ctypes.c_int32), ('map_off', ctypes.c_int32)]
 
 
+class NsBag(ctypes.Structure):
+    """``ot_ns_bag`` (include/onetrans_hip.h): one multi-valued NS feature of ``ot_ns_bag_pool`` /
+    ``ot_ns_bag_grad_pack``."""
+    _fields_ = [('table', c_void_p), ('ids', c_void_p), ('weights', c_void_p), ('row_offset', c_int64),
+                ('num_rows', c_int64), ('ids_stride', c_int64), ('weights_stride', c_int64),
+                ('width', ctypes.c_int32), ('cap', ctypes.c_int32), ('col', ctypes.c_int32),
+                ('pooling', ctypes.c_int32)]
+
+
+OT_BAG_SUM, OT_BAG_MEAN = 0, 1
+BAG_POOLINGS = {'sum': OT_BAG_SUM, 'mean': OT_BAG_MEAN}
+NS_BAG_MAX = 32              # ot_ns_bag_pool / ot_ns_bag_grad_pack: descriptors per call
+NS_BAG_MAX_WIDTH = 256       # ... and the widest row
 SEQ_TIME_MAX_L = 4096        # ot_seq_time_rows: events per sample (sorted in LDS)
 SEQ_TIME_MAX_SEQ = 32
 
@@ -174,11 +187,13 @@ SIGNATURES = {
     'ot_rank_topk': (c_int, [P, I64, c_int, P, c_int, P, I64, c_int, c_int, P, P, P, P, P, c_size_t, P]),
     'ot_seq_time_rows_workspace_size': (c_size_t, [c_int, c_int, c_int]),
     'ot_seq_time_rows': (c_int, [P, c_int, c_int, c_int, I64, P, P, P, P, c_size_t, P]),
+    'ot_ns_bag_pool': (c_int, [P, c_int, c_int, P, I64, P, P]),
+    'ot_ns_bag_grad_pack': (c_int, [P, c_int, c_int, P, I64, P, P, P, P]),
 }
 
-# ABI notes (mirrors include/onetrans_hip.h): the modes/flags above; the only struct is
+# ABI notes (mirrors include/onetrans_hip.h): the modes/flags above; the device-side struct is
 # ot_ns_field {const float* dense; const int64_t* ids; int64 row_offset; int64 stride; int col;
-# int width} = 40 bytes.
+# int width} = 40 bytes (the host-side descriptors are the ctypes Structures above: ot_seq_time 24, ot_ns_bag 72).
 NS_FIELD_BYTES = 40
 
 _lib = None

@@ -94,6 +94,11 @@ class OneTransConfig:
         self.seq_feature_dim = 64            # build: width of one sequence event (data_loader.py:146,322)
         self.ns_embedding_dim = 16           # build: per-field NS embedding width (Criteo shape)
         self.sparse_features: Dict[str, int] = {}   # build: NS id features -> cardinality
+        # build: multi-valued NS id features, pooled on the device into one NS column block each.
+        # name -> {'cardinality': N, 'pooling': 'sum' | 'mean'} (its own N rows of emb.ns, width ns_embedding_dim)
+        # or {'table': 'seq_item', 'pooling': ...} (rows of emb.seq_item, width seq_feature_dim); pooling
+        # defaults to 'mean'.  The input is an integer [B, cap] array, id < 0 or >= the row count = empty slot
+        self.bag_features: Dict[str, Dict] = {}
         self.seq_item_vocab = 0              # build: >0 => sequence features are item ids
         self.compute_dtype = 'fp32'          # build: arithmetic of the HIP path (reference is fp32)
         # build: the behaviour behind two reference flags the reference itself never reads
@@ -143,10 +148,26 @@ class OneTransConfig:
         fc = self.feature_config
         return list(fc['user_features']) + list(fc['item_features']) + list(fc['context_features'])
 
+    def ns_feature_width(self, name: str) -> int:
+        """Columns of one NS feature in the concat: 1 (dense), ns_embedding_dim (sparse id, or a bag over its own
+        rows of emb.ns), seq_feature_dim (a bag over emb.seq_item)."""
+        bag = getattr(self, 'bag_features', {}).get(name)
+        if bag is not None:
+            return self.seq_feature_dim if bag.get('table') == 'seq_item' else self.ns_embedding_dim
+        return self.ns_embedding_dim if name in self.sparse_features else 1
+
+    def bag_pooling(self, name: str) -> str:
+        return self.bag_features[name].get('pooling', 'mean')
+
+    def bag_rows(self, name: str) -> int:
+        """Row count a bag's ids are checked against: its cardinality, or seq_item_vocab."""
+        bag = self.bag_features[name]
+        return int(self.seq_item_vocab if bag.get('table') == 'seq_item' else bag['cardinality'])
+
     def ns_input_width(self, present: Optional[List[str]] = None) -> int:
-        """F_ns: 1 per dense feature, ns_embedding_dim per sparse-id feature."""
+        """F_ns: 1 per dense feature, ns_embedding_dim per sparse-id feature, the table width per bag feature."""
         names = self.ns_feature_names() if present is None else present
-        return sum(self.ns_embedding_dim if n in self.sparse_features else 1 for n in names)
+        return sum(self.ns_feature_width(n) for n in names)
 
     def seq_token_count(self, seq_lens: List[int]) -> int:
         """L_S = sum(L_i) + one [SEP] after every present sequence i < n-1 (model.py:266-272); no [SEP] under
@@ -296,6 +317,36 @@ def check_seq_fusion(cfg: OneTransConfig) -> None:
         raise ValueError("seq_fusion='time' needs a non-empty seq_time_suffix")
 
 
+BAG_POOLINGS = ('sum', 'mean')
+
+
+def check_bag_features(cfg: OneTransConfig) -> None:
+    """``bag_features``: every name is an NS feature that is not also in ``sparse_features``; each entry names
+    either a cardinality (own rows of emb.ns) or ``table='seq_item'`` (needs ``seq_item_vocab > 0``), and a
+    pooling of 'sum' or 'mean'."""
+    bags = getattr(cfg, 'bag_features', None) or {}
+    names = cfg.ns_feature_names()
+    for name, spec in bags.items():
+        if name in cfg.sparse_features:
+            raise ValueError(f'bag feature {name!r} is also in sparse_features')
+        if name not in names:
+            raise ValueError(f'bag feature {name!r} is in none of the user / item / context feature lists')
+        if not isinstance(spec, dict):
+            raise ValueError(f'bag feature {name!r}: a dict is expected, got {spec!r}')
+        pooling = spec.get('pooling', 'mean')
+        if pooling not in BAG_POOLINGS:
+            raise ValueError(f"bag feature {name!r}: unknown pooling {pooling!r}: expected 'sum' or 'mean'")
+        if 'table' in spec:
+            if spec['table'] != 'seq_item':
+                raise ValueError(f"bag feature {name!r}: unknown table {spec['table']!r}: expected 'seq_item'")
+            if 'cardinality' in spec:
+                raise ValueError(f"bag feature {name!r}: give either 'cardinality' or 'table', not both")
+            if not cfg.seq_item_vocab:
+                raise ValueError(f"bag feature {name!r}: table 'seq_item' needs seq_item_vocab > 0")
+        elif int(spec.get('cardinality', 0)) <= 0:
+            raise ValueError(f"bag feature {name!r}: needs a positive 'cardinality' or table='seq_item'")
+
+
 def workload_config(name: str) -> OneTransConfig:
     """Configs of BASELINE.json as OneTransConfig objects; ``cfg._seq_lens`` and
     ``cfg._batch`` carry the synthetic input shape."""
@@ -357,4 +408,4 @@ def algorithmic_flops_per_sample(cfg: OneTransConfig, seq_lens: List[int], f_ns:
 
 __all__ = ['OneTransConfig', 'OneTransSmallConfig', 'OneTransLargeConfig', 'get_model_config',
            'dense_optimizer_spec', 'DEFAULT_CONFIG', 'workload_config', 'algorithmic_flops_per_sample',
-           'CRITEO_CARDINALITIES']
+           'CRITEO_CARDINALITIES', 'check_bag_features']

@@ -16,6 +16,10 @@
   (``name + config.seq_time_suffix``, int64 ``[B, L_i]``) from a generator of their own, so every other array of a
   batch is bit-identical to the ``'sep'`` batch of the same seed.
 
+* ``bag_ids`` — when ``config.bag_features`` is set, ``criteo_batch`` also emits each bag feature's padded ids
+  (int64 ``[B, cap]``, ``-1`` = empty slot; Zipf ids, lengths from 0 to cap) and, for every other 'sum' bag,
+  per-slot weights ``name + '_weight'``; again from a generator of their own.
+
 All generators are numpy ``Generator(PCG64)``: same seed => same batch, here and
 on the GPU box.
 """
@@ -64,6 +68,41 @@ def seq_times(seed: int, B: int, names: List[str], lens: List[int], suffix: str 
     return out
 
 
+BAG_CAP = 8                         # default slots per sample of the synthetic bag features
+
+
+def bag_ids(seed: int, B: int, rows: int, cap: int, mean_fill: float = None) -> np.ndarray:
+    """One bag feature's padded ids: int64 [B, cap], sample b's first len_b slots hold ``Zipf(1.1) mod rows`` ids
+    (repeats inside a bag happen), the rest -1.  The lengths are binomial with mean ``mean_fill`` (default cap / 2),
+    so empty and full bags both occur; sample 0 is always empty and sample 1 (if any) full."""
+    rng = np.random.Generator(np.random.PCG64([int(seed), 0x626167]))
+    fill = cap / 2.0 if mean_fill is None else float(mean_fill)
+    lens = rng.binomial(cap, min(1.0, max(0.0, fill / cap)), size=B)
+    lens[0] = 0
+    if B > 1:
+        lens[1] = cap
+    ids = (rng.zipf(1.1, size=(B, cap)) - 1) % int(rows)
+    return np.where(np.arange(cap)[None, :] < lens[:, None], ids, -1).astype(np.int64)
+
+
+def _add_bags(ns: Dict[str, np.ndarray], config: OneTransConfig, seed: int, B: int, bags=None) -> None:
+    """``bags``: None (every configured bag feature, BAG_CAP slots), or {name: cap} / {name: (cap, mean fill)}."""
+    cfgd = getattr(config, 'bag_features', None) or {}
+    if not cfgd:
+        return
+    spec = {n: BAG_CAP for n in cfgd} if bags is None else dict(bags)
+    k = 0
+    for name in config.ns_feature_names():
+        if name not in cfgd or name not in spec:
+            continue
+        cap, fill = spec[name] if isinstance(spec[name], (tuple, list)) else (spec[name], None)
+        ns[name] = bag_ids(seed * 131 + k, B, config.bag_rows(name), int(cap), fill)
+        if config.bag_pooling(name) == 'sum' and k % 2 == 0:
+            wrng = np.random.Generator(np.random.PCG64([int(seed), 0x776774, k]))
+            ns[name + '_weight'] = wrng.uniform(0.25, 2.0, size=ns[name].shape).astype(np.float32)
+        k += 1
+
+
 def _add_times(seq: Dict[str, np.ndarray], config: OneTransConfig, seed: int) -> None:
     if getattr(config, 'seq_fusion', 'sep') != 'time' or not seq:
         return
@@ -99,8 +138,10 @@ def create_sample_batch(batch_size: int, config: OneTransConfig, seq_lens: Optio
 
 
 def criteo_batch(batch_size: int, config: OneTransConfig, seq_lens: Optional[List[int]] = None,
-                 seed: int = 1000, teacher: str = 'ids') -> Batch:
-    """Criteo-shape batch: dense I* float32 [B,1]; sparse C* int64 [B,1]; seqs int64 [B,L_i].
+                 seed: int = 1000, teacher: str = 'ids', bags=None) -> Batch:
+    """Criteo-shape batch: dense I* float32 [B,1]; sparse C* int64 [B,1]; seqs int64 [B,L_i]; the bag features of
+    ``config.bag_features`` int64 [B, cap] padded with -1 (``bags``: {name: cap} or {name: (cap, mean fill)};
+    default every bag feature with BAG_CAP slots; they do not enter the label signal).
 
     ``teacher`` picks the label signal: 'ids' (default; every feature, the sparse ids through a hashed
     per-id effect — learnable only by memorising ids) or 'dense' (the 13 dense features alone, 4x the
@@ -114,6 +155,8 @@ def criteo_batch(batch_size: int, config: OneTransConfig, seq_lens: Optional[Lis
     signal = np.zeros((B, 2))
     dense_signal = np.zeros((B, 2))
     for name in config.ns_feature_names():
+        if name in (getattr(config, 'bag_features', None) or {}):
+            continue                                   # drawn below, from a generator of their own
         if name in config.sparse_features:
             card = config.sparse_features[name]
             ids = (rng.zipf(1.1, size=(B, 1)) - 1) % card
@@ -132,6 +175,7 @@ def criteo_batch(batch_size: int, config: OneTransConfig, seq_lens: Optional[Lis
     for name, L in zip(fc['sequence_features'], lens):
         seq[name] = ((rng.zipf(1.1, size=(B, L)) - 1) % vocab).astype(np.int64)
     _add_times(seq, config, seed)
+    _add_bags(ns, config, seed, B, bags)
     if teacher == 'dense':
         signal = dense_signal
     elif teacher != 'ids':

@@ -84,6 +84,25 @@ class FeatureProcessor:
         return ids
 
 
+    @staticmethod
+    def pad_bags(lists, cap: Optional[int] = None) -> np.ndarray:
+        """Multi-valued id features (``config.bag_features``) as the model's padded input: ``lists`` holds one list
+        of ids per sample; returns int64 [B, cap] padded with -1 (an empty slot).  ``cap`` defaults to the longest
+        list (at least 1); a given ``cap`` truncates longer lists, keeping their tail (the most recent ids)."""
+        lists = [np.asarray(l, dtype=np.int64).reshape(-1) for l in lists]
+        if cap is None:
+            cap = max([len(l) for l in lists] + [1])
+        cap = int(cap)
+        if cap < 1:
+            raise ValueError(f'pad_bags: cap {cap} must be at least 1')
+        out = np.full((len(lists), cap), -1, dtype=np.int64)
+        for b, l in enumerate(lists):
+            n = min(len(l), cap)
+            if n:
+                out[b, :n] = l[len(l) - n:]
+        return out
+
+
 class SequenceProcessor:
     """data_loader.py:71-101."""
 

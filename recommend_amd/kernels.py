@@ -638,6 +638,41 @@ def rank_topk(probs, task_stride, T, weights, mode, req, C, R, K, top_idx, top_s
         _probe.end('rank', 0.0, ev)
 
 
+def ns_bag_descs(bags):
+    """The host descriptor array of ``ns_bag_pool`` / ``ns_bag_grad_pack``: ``bags`` = [dict(table, ids, weights,
+    row_offset, num_rows, ids_stride, weights_stride, width, cap, col, pooling)] with device tensors (or None for
+    ``weights``) and ``pooling`` 'sum' | 'mean'.  Build it once for buffers that persist (OneTransModel's plan)."""
+    arr = (_lib.NsBag * max(1, len(bags)))()
+    for k, b in enumerate(bags):
+        arr[k] = _lib.NsBag(ptr(b['table']), ptr(b['ids']), ptr(b.get('weights')), int(b['row_offset']),
+                            int(b['num_rows']), int(b['ids_stride']), int(b.get('weights_stride', 0)),
+                            int(b['width']), int(b['cap']), int(b['col']), _lib.BAG_POOLINGS[b['pooling']])
+    return arr
+
+
+def _bag_slice(descs, first: int, nbags: int):
+    return ctypes.cast(ctypes.byref(descs, first * ctypes.sizeof(_lib.NsBag)), ctypes.c_void_p) if nbags else None
+
+
+def ns_bag_pool(descs, nbags: int, B: int, out, ld_out: int, coef_out, first: int = 0) -> None:
+    """ot_ns_bag_pool over ``descs[first : first + nbags]``: each bag's pooled rows into its columns of ``out``
+    [B, ld_out]; ``coef_out`` (f32, sum of B * cap) receives the per-slot coefficients the backward reads."""
+    ev = _probe.begin() if _probe is not None else None
+    call('ot_ns_bag_pool', _bag_slice(descs, first, nbags), nbags, B, ptr(out), ld_out, ptr(coef_out), stream())
+    if ev is not None:
+        _probe.end('embedding', 0.0, ev)
+
+
+def ns_bag_grad_pack(descs, nbags: int, B: int, dmat, ld: int, coef, keys, grads, first: int = 0) -> None:
+    """ot_ns_bag_grad_pack over ``descs[first : first + nbags]`` (the bags of one table): keys (int64) and gradient
+    rows of every slot, bag-major; ``coef`` is the pool's ``coef_out`` at bag ``first``'s base."""
+    ev = _probe.begin() if _probe is not None else None
+    call('ot_ns_bag_grad_pack', _bag_slice(descs, first, nbags), nbags, B, ptr(dmat), ld, ptr(coef), ptr(keys),
+         ptr(grads), stream())
+    if ev is not None:
+        _probe.end('embedding', 0.0, ev)
+
+
 def seq_time_descs(seqs):
     """The host descriptor array of ``seq_time_rows``: ``seqs`` = [(times, stride_b, L, map_off)], ``times`` a device
     int64 tensor (or (tensor, element offset)).  Build it once for buffers that persist (OneTransModel's plan)."""

@@ -30,7 +30,7 @@ from . import kernels as K
 from ._lib import (OT_AX_BF16, OT_AX_BF16_RMSNORM, OT_AX_GELU, OT_AX_RMSNORM, OT_EPI_ACCUMULATE, OT_EPI_AUX_BF16, OT_EPI_BIAS,
                    OT_EPI_C_BF16, OT_EPI_DROPOUT, OT_EPI_GELU_BWD, OT_EPI_RESIDUAL, OT_EPI_RMSNORM_BWD,
                    OT_EPI_ROW_RSTD, OT_EPI_ROWDOT, OT_GEMM_NN, OT_GEMM_NT, OT_WG_D_BF16, NS_FIELD_BYTES)
-from .config import OneTransConfig, check_pyramid_select, check_seq_fusion, get_model_config
+from .config import OneTransConfig, check_bag_features, check_pyramid_select, check_seq_fusion, get_model_config
 from .layout import TILE, FlatLayout, RowMap, build_map, head_map, identity_map, layer_maps, round_up
 from .params import init_params, ns_table_offsets
 
@@ -50,7 +50,10 @@ class _Tokenize(torch.autograd.Function):
         # ---- NS tokens: gather/concat -> Dense(L_NS*d) straight into token rows L_S.. (model.py:253-254)
         if plan['ns_fields'] > 0:
             nsm = plan['nsmat']
-            K.ns_assemble(plan['ns_desc'], plan['ns_fields'], m.tables.get('emb.ns'), B, nsm, m.layout.f_pad)
+            if plan['ns_desc_n'] > 0:
+                K.ns_assemble(plan['ns_desc'], plan['ns_desc_n'], m.tables.get('emb.ns'), B, nsm, m.layout.f_pad)
+            if plan['n_bags'] > 0:                              # multi-valued features: pooled rows, same matrix
+                K.ns_bag_pool(plan['bag_descs'], plan['n_bags'], B, nsm, m.layout.f_pad, plan['bag_coef'])
             mp = plan['ns_map'].to(dev)
             K.gemm(OT_GEMM_NT, nsm, m.layout.f_pad, m.layout.f_pad, mp['rows'][0], m.pT('tok.ns.kernel'), 0,
                    m.layout.f_pad, m.cfg_Lnsd, mp['tile_group'], plan['ns_map'].ntiles, (x0, L_S * d), L0 * d,
@@ -93,17 +96,35 @@ class _Tokenize(torch.autograd.Function):
             K.wgrad(nsm, m.layout.f_pad, mp['rows'][0], (dx0, L_S * d), L0 * d, mp['rows'][0], m.layout.f_pad,
                     m.cfg_Lnsd, mp, plan['ns_map'].chunks.shape[0], 1, m.g('tok.ns.kernel'), 0, m.g('tok.ns.bias'),
                     0, accumulate=acc, device=dev, m_rows=B, rowmap=plan['ns_map'])
-            if plan['n_sparse'] > 0:
+            if plan['n_sparse'] > 0 or plan['n_bags'] > 0:
                 dns = torch.empty(B, m.layout.f_pad, device=dev)
                 K.gemm(OT_GEMM_NT, (dx0, L_S * d), L0 * d, m.cfg_Lnsd, mp['rows'][0], m.p('tok.ns.kernel'), 0,
                        m.cfg_Lnsd, m.layout.f_pad, mp['tile_group'], plan['ns_map'].ntiles, dns, m.layout.f_pad,
                        mp['rows'][0], m_rows=B)
                 e = m.config.ns_embedding_dim
-                n = plan['n_sparse'] * B
-                keys = torch.empty(n, dtype=torch.int64, device=dev)
-                grads = torch.empty(n, e, device=dev)
-                K.ns_grad_pack(plan['ns_desc'], plan['n_sparse'], e, dns, m.layout.f_pad, B, keys, grads)
-                m._pending_sparse.append(('emb.ns', keys, grads))
+                # one (keys, grads) pair per table: the single-id fields' B entries each, then every slot of the
+                # emb.ns bags; the emb.seq_item bags' slots are a second entry of that table (the optimizer joins
+                # the entries of one table before it de-duplicates)
+                n1 = plan['n_sparse'] * B
+                n = n1 + plan['bag_ns_slots']
+                if n > 0:
+                    keys = torch.empty(n, dtype=torch.int64, device=dev)
+                    grads = torch.empty(n, e, device=dev)
+                    if n1 > 0:
+                        K.ns_grad_pack(plan['ns_desc'], plan['n_sparse'], e, dns, m.layout.f_pad, B, keys, grads)
+                    if plan['n_bags_ns'] > 0:
+                        K.ns_bag_grad_pack(plan['bag_descs'], plan['n_bags_ns'], B, dns, m.layout.f_pad,
+                                           plan['bag_coef'], (keys, n1), (grads, n1 * e))
+                    m._pending_sparse.append(('emb.ns', keys, grads))
+                nq = plan['n_bags'] - plan['n_bags_ns']
+                if nq > 0:
+                    Eq = m.config.seq_feature_dim
+                    nslots = plan['bag_slots'] - plan['bag_ns_slots']
+                    keys = torch.empty(nslots, dtype=torch.int64, device=dev)
+                    grads = torch.empty(nslots, Eq, device=dev)
+                    K.ns_bag_grad_pack(plan['bag_descs'], nq, B, dns, m.layout.f_pad,
+                                       (plan['bag_coef'], plan['bag_ns_slots']), keys, grads, first=plan['n_bags_ns'])
+                    m._pending_sparse.append(('emb.seq_item', keys, grads))
         elif not acc:
             m.g('tok.ns.kernel').zero_()
             m.g('tok.ns.bias').zero_()
@@ -740,6 +761,7 @@ class OneTransModel(nn.Module):
             raise ValueError('head_dim must be 16, 32, 64 or 128')
         check_pyramid_select(cfg)
         check_seq_fusion(cfg)
+        check_bag_features(cfg)
         self.time_fusion = getattr(cfg, 'seq_fusion', 'sep') == 'time'
         # compute_dtype (build knob): 'fp32' (the reference's arithmetic: split or f32 GEMMs, ``matmul`` below),
         # 'bf16', or 'fp8attn' = BASELINE configs[4]'s attention on
@@ -960,6 +982,11 @@ class OneTransModel(nn.Module):
                     self.tables[name] = st.table
                     continue
                 if name.startswith('emb.'):
+                    # the gather kernels trust the configured row counts: a table of another shape (a checkpoint
+                    # of another config) is refused here instead of being read out of range
+                    want = self._table_shape(name)
+                    if want is not None and tuple(np.shape(arr)) != want:
+                        raise ValueError(f'{name}: loaded shape {tuple(np.shape(arr))} != {want} of this config')
                     self.tables[name] = torch.as_tensor(np.asarray(arr), dtype=torch.float32).to(self.device).contiguous()
                     continue
                 dst = self.p(name)
@@ -970,6 +997,14 @@ class OneTransModel(nn.Module):
                 else:
                     dst.copy_(src.reshape(dst.shape))
         self.refresh_shadow()
+
+    def _table_shape(self, name: str):
+        cfg = self.config
+        if name == 'emb.ns':
+            return (ns_table_offsets(cfg)['__total__'], cfg.ns_embedding_dim)
+        if name == 'emb.seq_item':
+            return (cfg.seq_item_vocab, cfg.seq_feature_dim)
+        return None
 
     def param_dict(self) -> Dict[str, np.ndarray]:
         """Host copies of every parameter.  With a row-sharded table this is a COLLECTIVE (the table
@@ -1005,8 +1040,8 @@ class OneTransModel(nn.Module):
         cfg = self.config
         gen = torch.Generator(device=self.device)
         gen.manual_seed(seed)
-        if cfg.sparse_features:
-            total = ns_table_offsets(cfg)['__total__']
+        total = ns_table_offsets(cfg)['__total__']
+        if total:
             t = torch.empty(total, cfg.ns_embedding_dim, device=self.device)
             t.uniform_(-0.05, 0.05, generator=gen)
             self.tables['emb.ns'] = t
@@ -1059,11 +1094,13 @@ class OneTransModel(nn.Module):
         present = [(i, n, int(seq[n].shape[1])) for i, n in enumerate(seq_names) if n in seq]
         ns_present = tuple(n for n in cfg.ns_feature_names() if n in ns)
         id_seq = bool(cfg.seq_item_vocab) and bool(present) and not torch.is_floating_point(torch.as_tensor(seq[present[0][1]]))
-        key = (B, tuple(present), ns_present, id_seq)
+        bags = self._bag_inputs(ns, ns_present, B) if cfg.bag_features else ()
+        key = (B, tuple(present), ns_present, id_seq) + ((tuple((n, cap, w is not None) for n, cap, _, w in bags),)
+                                                         if bags else ())
         times = self._seq_times(seq, present, B) if self.time_fusion and present else None
         plan = self._plans.get(key)
         if plan is None:
-            plan = self._build_plan(B, present, ns_present, id_seq)
+            plan = self._build_plan(B, present, ns_present, id_seq, bags)
             self._plans[key] = plan
         # ---- per-call data (copies into the plan's persistent buffers; no host sync)
         plan['gen'] += 1
@@ -1074,6 +1111,13 @@ class OneTransModel(nn.Module):
             if plan['n_sparse'] > 0:
                 plan['ids_buf'].copy_(torch.cat([ns[n].reshape(B, 1).to(dev, torch.int64)
                                                  for n in plan['sparse_names']], 1))
+            for (n, cap, ids, w), (ids_buf, w_buf) in zip(bags, plan['bag_bufs']):
+                ids_buf.copy_(ids)
+                if w_buf is not None:
+                    w_buf.copy_(w)
+            for k, tname in enumerate(plan.get('bag_tables', ())):
+                # (host descriptors: a table replaced since the plan was built, e.g. by load_weights, is followed)
+                plan['bag_descs'][k].table = self.tables[tname].data_ptr()
         if plan['seq_map'] is not None:
             if self.time_fusion:
                 # timestamp-aware fusion: stage the events' times and order each sample's events on the device;
@@ -1117,6 +1161,33 @@ class OneTransModel(nn.Module):
                 plan['seq_ids'] = None
         return plan
 
+    def _bag_inputs(self, ns, ns_present, B):
+        """The present bag features' inputs as (name, cap, ids [B, cap], weights [B, cap] or None): integer ids, and
+        optional float weights ``ns[name + '_weight']`` (pooling 'sum' only, as torch.nn.EmbeddingBag)."""
+        cfg = self.config
+        out = []
+        for n in ns_present:
+            if n not in cfg.bag_features:
+                continue
+            ids = ns[n]
+            ids = ids if isinstance(ids, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(ids))
+            if ids.is_floating_point() or ids.is_complex() or ids.dtype == torch.bool:
+                raise TypeError(f'bag feature {n!r}: integer ids are expected, got {ids.dtype}')
+            if ids.dim() != 2 or ids.shape[0] != B or ids.shape[1] < 1:
+                raise ValueError(f'bag feature {n!r}: ids of shape [B, cap] with cap >= 1 are expected, got '
+                                 f'{tuple(ids.shape)} (B = {B})')
+            w = ns.get(n + '_weight')
+            if w is not None:
+                if cfg.bag_pooling(n) != 'sum':
+                    raise ValueError(f"bag feature {n!r}: per-slot weights need pooling 'sum' (it is "
+                                     f'{cfg.bag_pooling(n)!r})')
+                w = w if isinstance(w, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(w))
+                if tuple(w.shape) != tuple(ids.shape) or not w.is_floating_point():
+                    raise ValueError(f'bag feature {n!r}: weights must be floats of the ids\' shape '
+                                     f'{tuple(ids.shape)}, got {w.dtype} {tuple(w.shape)}')
+            out.append((n, int(ids.shape[1]), ids, w))
+        return tuple(out)
+
     def _seq_times(self, seq, present, B) -> List[torch.Tensor]:
         """The present sequences' event times (``seq_fusion='time'``): ``seq[name + seq_time_suffix]``, an integer
         [B, L_name] host array or device tensor each."""
@@ -1137,7 +1208,7 @@ class OneTransModel(nn.Module):
             out.append(t)
         return out
 
-    def _build_plan(self, B, present, ns_present, id_seq):
+    def _build_plan(self, B, present, ns_present, id_seq, bags=()):
         cfg = self.config
         d = cfg.hidden_dim
         dev = self.device
@@ -1209,10 +1280,12 @@ class OneTransModel(nn.Module):
             plan['seq_map'] = None
         # ---- NS fields (model.py:243-253)
         offs = ns_table_offsets(cfg)
-        dense_names = [n for n in ns_present if n not in cfg.sparse_features]
+        dense_names = [n for n in ns_present if n not in cfg.sparse_features and n not in cfg.bag_features]
         sparse_names = [n for n in ns_present if n in cfg.sparse_features]
         plan.update(dense_names=dense_names, sparse_names=sparse_names, n_dense=len(dense_names),
-                    n_sparse=len(sparse_names), ns_fields=len(ns_present))
+                    n_sparse=len(sparse_names), ns_fields=len(ns_present),
+                    ns_desc_n=len(dense_names) + len(sparse_names), n_bags=0, n_bags_ns=0, bag_bufs=[],
+                    bag_slots=0, bag_ns_slots=0)
         plan['nsmat'] = torch.zeros(B, self.layout.f_pad, device=dev)
         if ns_present:
             plan['dense_buf'] = torch.zeros(B, max(1, len(dense_names)), device=dev)
@@ -1222,9 +1295,10 @@ class OneTransModel(nn.Module):
             c = 0
             for n in ns_present:
                 col[n] = c
-                c += cfg.ns_embedding_dim if n in cfg.sparse_features else 1
-            recs = np.zeros(len(ns_present), dtype=np.dtype([('dense', '<u8'), ('ids', '<u8'), ('row_offset', '<i8'),
-                                                             ('stride', '<i8'), ('col', '<i4'), ('width', '<i4')]))
+                c += cfg.ns_feature_width(n)
+            recs = np.zeros(max(1, plan['ns_desc_n']),
+                            dtype=np.dtype([('dense', '<u8'), ('ids', '<u8'), ('row_offset', '<i8'),
+                                            ('stride', '<i8'), ('col', '<i4'), ('width', '<i4')]))
             assert recs.dtype.itemsize == NS_FIELD_BYTES
             k = 0
             for j, n in enumerate(sparse_names):
@@ -1236,7 +1310,46 @@ class OneTransModel(nn.Module):
                 k += 1
             plan['ns_desc'] = torch.from_numpy(recs.view(np.uint8).copy()).to(dev)
             plan['ns_map'] = identity_map(B)
+            if bags:
+                self._plan_bags(plan, B, bags, col, offs)
         return plan
+
+    def _plan_bags(self, plan, B, bags, col, offs) -> None:
+        """The plan's bag features: persistent staging buffers for the ids (and weights), the host
+        descriptors of ot_ns_bag_pool / ot_ns_bag_grad_pack — the emb.ns bags first, then the emb.seq_item bags,
+        so each table's bags are one run of descriptors and of coefficient slots — and the coefficient buffer."""
+        cfg, dev = self.config, self.device
+        import torch.distributed as dist
+        if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
+            raise NotImplementedError('bag_features: data-parallel runs (world size > 1) are not supported (the '
+                                      'sparse all-gather and the early dense exchange are not exercised with bags)')
+        if len(bags) > _lib.NS_BAG_MAX:
+            raise ValueError(f'bag_features: {len(bags)} bag features in one batch, at most {_lib.NS_BAG_MAX}')
+        is_seq = lambda n: cfg.bag_features[n].get('table') == 'seq_item'
+        if any(is_seq(n) for n, _, _, _ in bags) and 'emb.seq_item' in self.sharded:
+            raise NotImplementedError("bag_features: a 'seq_item' bag with a row-sharded emb.seq_item table is not "
+                                      "supported (the bag gathers local rows); use table_sharding='none'")
+        order = sorted(range(len(bags)), key=lambda i: is_seq(bags[i][0]))          # stable: emb.ns bags first
+        bufs = [None] * len(bags)
+        recs = []
+        for i in order:
+            n, cap, _, w = bags[i]
+            E = cfg.ns_feature_width(n)
+            if E % 4 or E > _lib.NS_BAG_MAX_WIDTH:
+                raise ValueError(f'bag feature {n!r}: row width {E} must be a multiple of 4, at most '
+                                 f'{_lib.NS_BAG_MAX_WIDTH}')
+            ids_buf = torch.full((B, cap), -1, dtype=torch.int64, device=dev)
+            w_buf = torch.zeros(B, cap, device=dev) if w is not None else None
+            bufs[i] = (ids_buf, w_buf)
+            recs.append(dict(table=self.tables['emb.seq_item' if is_seq(n) else 'emb.ns'], ids=ids_buf, weights=w_buf,
+                             row_offset=0 if is_seq(n) else offs[n], num_rows=cfg.bag_rows(n), ids_stride=cap,
+                             weights_stride=cap, width=E, cap=cap, col=col[n], pooling=cfg.bag_pooling(n)))
+        n_ns = sum(1 for i in order if not is_seq(bags[i][0]))
+        slots = [B * r['cap'] for r in recs]
+        plan.update(n_bags=len(bags), n_bags_ns=n_ns, bag_bufs=bufs, bag_slots=sum(slots),
+                    bag_ns_slots=sum(slots[:n_ns]), bag_descs=K.ns_bag_descs(recs),
+                    bag_tables=['emb.seq_item' if is_seq(bags[i][0]) else 'emb.ns' for i in order],
+                    bag_coef=torch.zeros(max(1, sum(slots)), device=dev))
 
     # ---------------------------------------------------------------- forward
     def forward(self, non_seq_features, seq_features=None, training: bool = False,

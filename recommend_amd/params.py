@@ -21,7 +21,8 @@ out_norm               [d]                              OneTransModel.output_nor
 head.w1, head.b1       [T, d, d/2], [T, d/2]            task_heads[task] Dense(d/2, gelu) (model.py:325-330)
 head.w2, head.b2       [T, d/2], [T]                    task_heads[task] Dense(1, sigmoid)
 emb.ns                 [sum(card), e]                   build extension: NS id -> row; the per-field tables
-                                                        are concatenated (row offset ns_table_offsets())
+                                                        (single-id and bag features) are concatenated (row
+                                                        offset ns_table_offsets())
 emb.seq_item           [vocab, E]                       build extension: seq item id -> row
 =====================  ===============================  ==============================================
 
@@ -68,12 +69,18 @@ def dense_param_shapes(cfg: OneTransConfig, f_ns: int) -> Dict[str, Tuple[int, .
 
 
 def ns_table_offsets(cfg: OneTransConfig) -> Dict[str, int]:
-    """Row offset of every NS id feature inside the concatenated 'emb.ns' table."""
+    """Row offset of every NS id feature inside the concatenated 'emb.ns' table: the single-id features of
+    ``sparse_features`` and the bag features that own rows (``bag_features[name]['cardinality']``), in
+    ``ns_feature_names()`` order."""
     off, out = 0, {}
+    bags = getattr(cfg, 'bag_features', None) or {}
     for name in cfg.ns_feature_names():
         if name in cfg.sparse_features:
             out[name] = off
             off += cfg.sparse_features[name]
+        elif name in bags and bags[name].get('table') != 'seq_item':
+            out[name] = off
+            off += int(bags[name]['cardinality'])
     out['__total__'] = off
     return out
 
@@ -130,8 +137,8 @@ def init_tables(cfg: OneTransConfig, seed: int) -> Dict[str, np.ndarray]:
     """Embedding tables, Keras Embedding init U(-0.05, 0.05) (host float64; small configs only)."""
     rng = np.random.Generator(np.random.PCG64(seed))
     T = {}
-    if cfg.sparse_features:
-        total = ns_table_offsets(cfg)['__total__']
+    total = ns_table_offsets(cfg)['__total__']
+    if total:
         T['emb.ns'] = rng.uniform(-0.05, 0.05, size=(total, cfg.ns_embedding_dim))
     if cfg.seq_item_vocab:
         T['emb.seq_item'] = rng.uniform(-0.05, 0.05, size=(cfg.seq_item_vocab, cfg.seq_feature_dim))

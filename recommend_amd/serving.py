@@ -404,10 +404,26 @@ class OneTransInferenceEngine:
                for k, v in sequence_features.items()}
         return non_seq, seq
 
+    def _is_bag(self, name: str) -> bool:
+        bags = getattr(self.config, 'bag_features', None) or {}
+        return name in bags or (name.endswith('_weight') and name[:-len('_weight')] in bags)
+
+    def _ns_tensor(self, name: str, v, dev):
+        """One NS input on the device: [B, 1], or a bag feature's padded [B, cap] ids / weights as they are."""
+        import numpy as np
+        if self._is_bag(name):
+            t = torch.as_tensor(np.asarray(v))
+            if t.dim() != 2:                           # one sample's Python list of ids (or of weights)
+                from .features import FeatureProcessor
+                t = (torch.from_numpy(FeatureProcessor.pad_bags([v])) if name in self.config.bag_features
+                     else t.to(torch.float32).reshape(1, -1))
+            return t.to(dev)
+        return torch.as_tensor(np.asarray(v)).reshape(-1, 1).to(dev)
+
     def _predict(self, non_seq, seq):
         import numpy as np
         dev = self.model.device
-        ns = {k: torch.as_tensor(np.asarray(v)).reshape(-1, 1).to(dev) for k, v in non_seq.items()}
+        ns = {k: self._ns_tensor(k, v, dev) for k, v in non_seq.items()}
         sq = {k: torch.as_tensor(np.asarray(v)).to(dev) for k, v in seq.items()}
         with torch.no_grad():
             out = self.model((ns, sq), training=False)
@@ -434,7 +450,10 @@ class OneTransInferenceEngine:
         t0 = time.time()
         try:
             pre = [self.preprocess_input(*b) for b in batch_data]
-            ns = {k: np.concatenate([np.asarray(p[0][k]).reshape(-1) for p in pre]) for k in pre[0][0]}
+            from .features import FeatureProcessor
+            bags = getattr(self.config, 'bag_features', None) or {}
+            ns = {k: (FeatureProcessor.pad_bags([p[0][k] for p in pre]) if k in bags
+                      else np.concatenate([np.asarray(p[0][k]).reshape(-1) for p in pre])) for k in pre[0][0]}
             seq = {k: np.stack([p[1][k] for p in pre]) for k in pre[0][1]}
             out = self._predict(ns, seq)
             n = len(batch_data)
@@ -451,11 +470,27 @@ class OneTransInferenceEngine:
         _, seq = self.preprocess_input({}, {}, {}, sequence_features)
         cache = self.server.encode_requests({k: torch.as_tensor(v[None]).to(dev) for k, v in seq.items()})
         ns = {}
+        from .features import FeatureProcessor
+        bags = getattr(self.config, 'bag_features', None) or {}
+        C = len(candidates)
         for k, v in user_features.items():
-            ns[k] = np.repeat(np.asarray(v).reshape(-1)[:1], len(candidates))
+            if k in bags:                              # a request-level bag: one id list, shared by the candidates
+                ns[k] = np.repeat(FeatureProcessor.pad_bags([v]), C, axis=0)
+            else:
+                ns[k] = np.repeat(np.asarray(v).reshape(-1)[:1], C)
         for k in candidates[0]:
-            ns[k] = np.concatenate([np.asarray(c[k]).reshape(-1) for c in candidates])
-        return cache, {k: torch.as_tensor(v).reshape(-1, 1).to(dev) for k, v in ns.items()}
+            if k in bags:                              # a candidate-level bag: each candidate's Python list of ids
+                ns[k] = FeatureProcessor.pad_bags([c[k] for c in candidates])
+            elif self._is_bag(k):                      # its per-slot weights, padded like the ids (tail kept)
+                cap = max([len(c[k]) for c in candidates] + [1])
+                w = np.zeros((C, cap), dtype=np.float32)
+                for i, c in enumerate(candidates):
+                    if len(c[k]):
+                        w[i, :len(c[k])] = np.asarray(c[k], dtype=np.float32)
+                ns[k] = w
+            else:
+                ns[k] = np.concatenate([np.asarray(c[k]).reshape(-1) for c in candidates])
+        return cache, {k: self._ns_tensor(k, v, dev) for k, v in ns.items()}
 
     def score_candidates(self, user_features: Dict, sequence_features: Dict, candidates: List[Dict]):
         """One request (user + sequences), many candidates (item / context features each): stage I once,

@@ -295,8 +295,27 @@ class OneTransOptimizer:
                 return g, otdist.allreduce_sum_async(cg), idx, cg
         return g, otdist.allreduce_sum_async(g), None, None
 
+    @staticmethod
+    def _join_pending(pending):
+        """One (keys, grads) per table: entries naming the same table (a 'seq_item' bag next to the S sequences; the
+        two plans of a request-grouped step) are concatenated, so the table gets one de-duplicated gradient, one
+        clip and one Adagrad application.  A table with a single entry keeps its tensors as they are."""
+        names = [name for (name, _, _) in pending]
+        if len(set(names)) == len(names):
+            return pending
+        out = []
+        for name in dict.fromkeys(names):
+            ent = [(k, g) for (n, k, g) in pending if n == name]
+            if len(ent) == 1:
+                out.append((name, ent[0][0], ent[0][1]))
+            else:
+                out.append((name, torch.cat([k.reshape(-1) for k, _ in ent]),
+                            torch.cat([g.reshape(-1, g.shape[-1]) for _, g in ent])))
+        return out
+
     def step(self) -> None:
         m = self.model
+        m._pending_sparse = self._join_pending(m._pending_sparse)
         # replicated tables small enough to exchange densely: scatter the de-duplicated gradient and
         # start its all-reduce first, so the dense optimizer below runs while it is in flight
         early = {}
