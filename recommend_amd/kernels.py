@@ -445,23 +445,21 @@ def attn_bwd(qkv, ld, out, dout, lse, B, H, I, K, hd, dqkv, qpos=None, dq_part_b
         _probe.end('attention', 8.0 * (K * I - K * (K - 1) / 2) * hd * H * B, ev, f'bwd I{I} K{K} hd{hd}')
 
 
-def attn_fwd_cached(qkv, ld, kv_cache, ldc, req, C, H, Ic, n, Kq, hd, out) -> None:
-    """ot_attn_fwd_cached: N-side queries over a request's cached S-side K/V plus their own rows."""
+def attn_fwd_cached(qkv, ld, kv_cache, ldc, req, C, H, Ic, n, Kq, hd, out, lse=None) -> None:
+    """ot_attn_fwd_cached: N-side queries over a request's cached S-side K/V plus their own rows; given ``lse``
+    [C, H, Kq], ot_attn_fwd_cached_lse: the same forward, which also writes lse for the backward."""
     ev = _probe.begin() if _probe is not None else None
-    call('ot_attn_fwd_cached', ptr(qkv), ld, ptr(kv_cache), ldc, ptr(req), C, H, Ic, n, Kq, hd, ptr(out), stream())
+    args = (ptr(qkv), ld, ptr(kv_cache), ldc, ptr(req), C, H, Ic, n, Kq, hd, ptr(out))
+    if lse is None:
+        call('ot_attn_fwd_cached', *args, stream())
+    else:
+        call('ot_attn_fwd_cached_lse', *args, ptr(lse), stream())
     if ev is not None:
         _probe.end('attention', 4.0 * (Kq * (Ic + n) - Kq * (Kq - 1) / 2) * hd * H * C, ev,
-                   f'fwd_cached Ic{Ic} n{n} K{Kq} hd{hd}')
+                   f'fwd_cached{"" if lse is None else "_lse"} Ic{Ic} n{n} K{Kq} hd{hd}')
 
 
-def attn_fwd_cached_lse(qkv, ld, kv_cache, ldc, req, C, H, Ic, n, Kq, hd, out, lse) -> None:
-    """ot_attn_fwd_cached_lse: attn_fwd_cached that also writes lse [C, H, Kq] for the backward."""
-    ev = _probe.begin() if _probe is not None else None
-    call('ot_attn_fwd_cached_lse', ptr(qkv), ld, ptr(kv_cache), ldc, ptr(req), C, H, Ic, n, Kq, hd, ptr(out),
-         ptr(lse), stream())
-    if ev is not None:
-        _probe.end('attention', 4.0 * (Kq * (Ic + n) - Kq * (Kq - 1) / 2) * hd * H * C, ev,
-                   f'fwd_cached_lse Ic{Ic} n{n} K{Kq} hd{hd}')
+attn_fwd_cached_lse = attn_fwd_cached    # the name tests/test_request_attn_gpu.py calls the lse form by
 
 
 def attn_bwd_cached(qkv, ld, kv_cache, ldc, req_start, R, C, H, Ic, n, Kq, hd, out, dout, lse, dqkv, dkv_cache,

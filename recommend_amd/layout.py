@@ -250,7 +250,7 @@ def layer_maps(cfg: OneTransConfig, B: int, I: int, K: int, p0: int = 0,
     * ``tail``: the kept tokens; space 0 = token rows b*I + p in the input, space 1 = compact
       rows b*K + j (p = I - K + j): Q projection (K < I), Wo, FFN.
 
-    ``p0`` / ``I_full`` (serving, recommend_amd/serving.py): the I rows are the span of positions
+    ``p0`` / ``I_full`` (the two-stage paths, recommend_amd/span_block.py): the I rows are the span of positions
     p0 .. p0+I-1 of a layer with I_full tokens, so a row's weight group is
     group_of_position(p0 + p, I_full).
     """

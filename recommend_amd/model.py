@@ -1056,10 +1056,13 @@ class OneTransModel(nn.Module):
         return [self.flat] + list(self.tables.values())
 
     # ---------------------------------------------------------------- row maps (cached)
-    def maps(self, B, I, Kq):
-        key = (B, I, Kq)
+    def maps(self, B, I, Kq, p0=0, I_full=0):
+        """Row maps of a block on B samples of I tokens keeping Kq; ``p0`` / ``I_full``: the I rows are the span of
+        positions p0.. of a layer of I_full tokens (layout.layer_maps).  A span that is the whole layer shares the
+        layer's maps."""
+        key = (B, I, Kq) if p0 == 0 and I_full in (0, I) else (B, I, Kq, p0, I_full)
         if key not in self._maps:
-            self._maps[key] = layer_maps(self.config, B, I, Kq)
+            self._maps[key] = layer_maps(self.config, B, I, Kq, p0=p0, I_full=I_full)
         return self._maps[key]
 
     def head_rows(self, B):

@@ -27,11 +27,9 @@ from typing import Dict
 import torch
 
 from . import kernels as K
-from ._lib import (OT_AX_GELU, OT_AX_RMSNORM, OT_EPI_BIAS, OT_EPI_DROPOUT, OT_EPI_GELU_BWD, OT_EPI_RESIDUAL,
-                   OT_GEMM_NT)
-from .layout import layer_maps
-from .model import RMS_EPS, _Head, _Tokenize, _wgrad_single, layer_seed
-from .serving import request_schedule
+from ._lib import OT_AX_GELU, OT_AX_RMSNORM, OT_EPI_GELU_BWD, OT_GEMM_NT
+from .model import _Head, _Tokenize, _wgrad_single, layer_seed
+from .span_block import check_req, request_schedule, s_rows, s_rows_grad, span_forward
 
 N_SEED_OFFSET = 0x632BE5AB        # odd: the N span's dropout seed is the layer seed plus this (mod 2^32)
 
@@ -58,13 +56,6 @@ def check_supported(m) -> None:
         raise NotImplementedError('forward_requests: data-parallel runs (world size > 1) are not supported')
 
 
-def _span_maps(m, B, I, Kq, p0, I_full):
-    key = ('span', B, I, Kq, p0, I_full)
-    if key not in m._aux_maps:
-        m._aux_maps[key] = layer_maps(m.config, B, I, Kq, p0=p0, I_full=I_full)
-    return m._aux_maps[key]
-
-
 # =============================================================================== tokenizer
 class _TokenizeRequests(torch.autograd.Function):
     """R requests' S tokens (the S-only plan) and C candidates' NS tokens (the NS-only plan) as one autograd
@@ -74,26 +65,19 @@ class _TokenizeRequests(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, flat, m, plan_s, plan_n):
-        d = m.config.hidden_dim
         cs, cn = SimpleNamespace(), SimpleNamespace()
         x0s = _Tokenize.forward(cs, flat, m, plan_s)            # [R*L0, d]; the NS rows are zero
         xn = _Tokenize.forward(cn, flat, m, plan_n)             # [C*L_NS, d]
-        R, L0, L_S = plan_s['B'], plan_s['L0'], plan_s['L_S']
-        xs = x0s.view(R, L0, d)[:, :L_S].reshape(R * L_S, d)
         ctx.m, ctx.cs, ctx.cn = m, cs, cn
-        return xs, xn
+        return s_rows(x0s, plan_s), xn
 
     @staticmethod
     def backward(ctx, dxs, dxn):
         m, cs, cn = ctx.m, ctx.cs, ctx.cn
         with K.precision(m.matmul):
-            d = m.config.hidden_dim
-            R, L0, L_S = cs.plan['B'], cs.plan['L0'], cs.plan['L_S']
-            dx0 = torch.zeros(R, L0, d, device=dxs.device)
-            dx0[:, :L_S] = dxs.reshape(R, L_S, d)
             # the S plan first: it writes tok.seq.* / tok.sep and (no NS fields) clears tok.ns.* unless the
             # model accumulates; the N plan then adds its tok.ns.* and leaves the absent sequence parts alone
-            _Tokenize._backward(cs, dx0.view(R * L0, d))
+            _Tokenize._backward(cs, s_rows_grad(dxs, cs.plan))
             pending = m._pending_sparse
             acc = m.accumulate_grads
             m.accumulate_grads = True
@@ -121,66 +105,22 @@ class _SpanBlock(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, flat, x, kv, m, l, span, B, I, Kq, p0, I_full, seed, training, req, req_start, R, state):
-        cfg = m.config
-        d, f, H = cfg.hidden_dim, cfg.ffn_dim, cfg.num_heads
-        hd = d // H
-        dev = x.device
         cached = span == 'N'
-        mp = _span_maps(m, B, I, max(Kq, 1), p0, I_full)
-        ma, mt = mp['all'].to(dev), mp['tail'].to(dev)
-        na, nt = mp['all'].ntiles, mp['tail'].ntiles
-        rate = cfg.dropout_rate if training else 0.0
-        dflag = OT_EPI_DROPOUT if rate > 0 else 0
-        tail = (Kq, I)
-        wqkv, wo = m.pT(f'blk.{l}.wqkv'), m.pT(f'blk.{l}.wo')
-        w1, b1, w2, b2 = m.pT(f'blk.{l}.w1'), m.p(f'blk.{l}.b1'), m.pT(f'blk.{l}.w2'), m.p(f'blk.{l}.b2')
-        g1, g2 = m.p(f'blk.{l}.norm1'), m.p(f'blk.{l}.norm2')
-        rstd1 = torch.empty(B * I, device=dev)
-        K.rmsnorm_fwd(x, d, B * I, d, rstd1, eps=RMS_EPS)
-        qkv = torch.empty(B * I, 3 * d, device=dev)
-        if Kq < I:
-            qkv[:, :d].zero_()                       # rows without a query
-        # K/V for every row (weight cols d..3d of each group's [d, 3d] bank), Q for the kept rows
-        K.gemm(OT_GEMM_NT, x, d, d, ma['rows'][0], (wqkv, d * d), 3 * d * d, d, 2 * d, ma['tile_group'], na,
-               (qkv, d), 3 * d, ma['rows'][0], a_xform=OT_AX_RMSNORM, rstd=rstd1, gamma=g1, m_rows=mp['all'].nrows)
+        rate = m.config.dropout_rate if training else 0.0
+        x2, qkv, saved = span_forward(m, l, x, B, I, Kq, p0, I_full, cached=cached, kv=kv, req=req, R=R, seed=seed,
+                                      rate=rate, for_backward=True)
         ctx.m, ctx.l, ctx.span, ctx.dims = m, l, span, (B, I, Kq, p0, I_full, R)
         ctx.seed, ctx.rate, ctx.state = seed, rate, state
         ctx.has_kv = kv is not None
         if Kq == 0:
-            ctx.save_for_backward(x, rstd1)
+            ctx.save_for_backward(*saved)
             x2 = x.new_empty(0)
             ctx.mark_non_differentiable(x2)
             return x2, qkv
-        K.gemm(OT_GEMM_NT, x, d, d, mt['rows'][0], wqkv, 3 * d * d, d, d, mt['tile_group'], nt, qkv, 3 * d,
-               mt['rows'][0], a_xform=OT_AX_RMSNORM, rstd=rstd1, gamma=g1, m_rows=mp['tail'].nrows)
-        o = torch.empty(B * Kq, d, device=dev)
-        lse = torch.empty(B * H * Kq, device=dev)
         if cached:
-            Ic = kv.shape[0] // R if kv is not None else 0
-            K.attn_fwd_cached_lse(qkv, 3 * d, (kv, d) if kv is not None else None, 3 * d, req, B, H, Ic, I, Kq, hd,
-                                  o, lse)
-        else:
-            K.attn_fwd(qkv, 3 * d, B, H, I, Kq, hd, o, lse)
-        # x1 = x[tail] + drop(o @ Wo)
-        x1 = torch.empty(B * Kq, d, device=dev)
-        K.gemm(OT_GEMM_NT, o, d, d, mt['rows'][1], wo, 0, d, d, mt['tile_group'], nt, x1, d, mt['rows'][1],
-               epi=OT_EPI_RESIDUAL | dflag, res=x, ldres=d, res_tok=1, seed=seed, site=2 * l, drop=rate, tail=tail,
-               m_rows=mp['tail'].nrows)
-        rstd2 = torch.empty(B * Kq, device=dev)
-        K.rmsnorm_fwd(x1, d, B * Kq, d, rstd2, eps=RMS_EPS)
-        # u = norm2(x1) @ W1[g] + b1[g]; x2 = x1 + drop(gelu(u) @ W2[g] + b2[g])
-        u = torch.empty(B * Kq, f, device=dev)
-        K.gemm(OT_GEMM_NT, x1, d, d, mt['rows'][1], w1, d * f, d, f, mt['tile_group'], nt, u, f, mt['rows'][1],
-               a_xform=OT_AX_RMSNORM, rstd=rstd2, gamma=g2, bias=b1, bias_gstride=f, epi=OT_EPI_BIAS,
-               m_rows=mp['tail'].nrows)
-        x2 = torch.empty(B * Kq, d, device=dev)
-        K.gemm(OT_GEMM_NT, u, f, f, mt['rows'][1], w2, f * d, f, d, mt['tile_group'], nt, x2, d, mt['rows'][1],
-               a_xform=OT_AX_GELU, bias=b2, bias_gstride=d, epi=OT_EPI_BIAS | OT_EPI_RESIDUAL | dflag, res=x1,
-               ldres=d, res_tok=0, seed=seed, site=2 * l + 1, drop=rate, tail=tail, m_rows=mp['tail'].nrows)
-        if cached:
-            ctx.save_for_backward(x, rstd1, qkv, o, lse, x1, rstd2, u, req_start, *([kv] if kv is not None else []))
+            ctx.save_for_backward(*saved, req_start, *([kv] if kv is not None else []))
             return x2
-        ctx.save_for_backward(x, rstd1, qkv, o, lse, x1, rstd2, u)
+        ctx.save_for_backward(*saved)
         return x2, qkv
 
     @staticmethod
@@ -202,7 +142,7 @@ class _SpanBlock(torch.autograd.Function):
         written = ctx.state['written']
         acc = m.accumulate_grads or l in written
         written.add(l)
-        mp = _span_maps(m, B, I, max(Kq, 1), p0, I_full)
+        mp = m.maps(B, I, max(Kq, 1), p0, I_full)
         tail = (Kq, I)
         dkv = None
         if Kq == 0:
@@ -282,26 +222,6 @@ class _SpanBlock(torch.autograd.Function):
 
 
 # =============================================================================== the model path
-def validate_req(req, R: int, C: int) -> None:
-    """``req`` [C]: non-decreasing request indices in [0, R).  One small read-back, before any launch (the
-    kernels index the K/V rows with req unchecked)."""
-    t = torch.as_tensor(req)
-    if t.dim() != 1 or t.numel() != C:
-        raise ValueError(f'forward_requests: req has shape {tuple(t.shape)}, expected ({C},) — one request index '
-                         'per candidate')
-    if t.is_floating_point() or t.dtype == torch.bool:
-        raise ValueError(f'forward_requests: req is {t.dtype}; integer request indices are expected')
-    if C == 0:
-        return
-    t = t.to(torch.int64)
-    lo, hi, unsorted = (int(v) for v in torch.stack([t.min(), t.max(), (t[1:] < t[:-1]).sum()]).cpu())
-    if lo < 0 or hi >= R:
-        raise ValueError(f'forward_requests: request index out of range [0, {R}) (min {lo}, max {hi})')
-    if unsorted:
-        raise ValueError(f'forward_requests: req must be non-decreasing (candidates grouped by request); '
-                         f'{unsorted} descent(s)')
-
-
 def forward_probs_requests(m, ns: Dict, seq: Dict, req, training: bool = False, validate: bool = True):
     """[T, C] probabilities (``_ot_logits`` set, like ``forward_probs``) of C candidates (``ns``, C rows) of R
     requests (``seq``, R rows), ``req`` [C] the request of each candidate."""
@@ -314,7 +234,7 @@ def forward_probs_requests(m, ns: Dict, seq: Dict, req, training: bool = False, 
     C = int(next(iter(ns.values())).shape[0])
     R = int(next(iter(seq.values())).shape[0])
     if validate:
-        validate_req(req, R, C)
+        check_req('forward_requests', req, R, C, ordered=True)
     elif torch.as_tensor(req).numel() != C:
         raise ValueError(f'forward_requests: {torch.as_tensor(req).numel()} request indices for {C} candidates')
     if C == 0 or R == 0:

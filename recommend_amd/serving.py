@@ -18,7 +18,7 @@ model and the CPU oracle.  Pyramid keeps (tail, model.py:296/371 with the D2 fix
 dead-code elimination carry over: at layer l the kept tail of K_l tokens splits into S rows (computed
 in stage I) and N rows (stage II).  Inference only (no dropout).  Positions restart in every layer,
 so every row's weight group is the one of its position in the full layer input
-(``layout.layer_maps(p0=, I_full=)``).
+(``OneTransModel.maps(p0=, I_full=)``).
 
 Cross-request reuse (``extend_requests``): new behaviours appended to the LAST configured sequence
 extend the S side at its end, so with no pruning before the last layer only the new tokens are computed
@@ -36,25 +36,8 @@ from typing import Dict, List, Optional
 import torch
 
 from . import kernels as K
-from ._lib import (OT_AX_GELU, OT_AX_RMSNORM, OT_EPI_BIAS, OT_EPI_RESIDUAL, OT_GEMM_NT, OneTransHipError)
-from .layout import layer_maps
-
-RMS_EPS = 1e-6
-
-
-def request_schedule(cfg, L_S: int) -> List[Dict]:
-    """The two-stage split of every layer (serving and request-grouped training): S rows s, N rows n, kept S
-    rows kS, kept N rows kN (kS + kN = the layer's keep; the tail keep takes the N rows first)."""
-    L_NS = cfg.num_ns_tokens
-    sched = cfg.pyramid_schedule(L_S + L_NS)
-    out, s, n = [], L_S, L_NS
-    for l, e in enumerate(sched):
-        keep = e['keep'] if l < len(sched) - 1 else 1        # only the last token is read (model.py:390)
-        kN = min(keep, n)
-        kS = keep - kN
-        out.append({'I': s + n, 's': s, 'n': n, 'kS': kS, 'kN': kN})
-        s, n = kS, kN
-    return out
+from ._lib import OneTransHipError
+from .span_block import check_req, request_schedule, s_rows, span_forward
 
 
 class RequestCache:
@@ -78,7 +61,6 @@ class OneTransServer:
         if getattr(cfg, 'pyramid_select', 'tail') != 'tail':
             raise ValueError("OneTransServer: pyramid_select must be 'tail' (a score-based keep would depend on "
                              "the NS tokens' positions in every layer)")
-        self._maps = {}
 
     # ------------------------------------------------------------------ schedule
 
@@ -86,55 +68,10 @@ class OneTransServer:
     def precision_model(self):
         """The model whose arithmetic the cached stages run in (kernels.in_model_precision)."""
         return self.m
+
     def schedule(self, L_S: int) -> List[Dict]:
         """Per layer: S rows s, N rows n, kept S rows kS, kept N rows kN (kS + kN = the layer's keep)."""
         return request_schedule(self.m.config, L_S)
-
-    def _layer_maps(self, B, I, Kq, p0, I_full):
-        key = (B, I, Kq, p0, I_full)
-        if key not in self._maps:
-            self._maps[key] = layer_maps(self.m.config, B, I, Kq, p0=p0, I_full=I_full)
-        return self._maps[key]
-
-    # ------------------------------------------------------------------ one block (forward only)
-    def _block(self, l: int, x: torch.Tensor, B: int, I: int, Kq: int, p0: int, I_full: int, attn):
-        """OneTransBlock.call (model.py:186-200) on B spans of I rows (positions p0.. of a layer of I_full
-        tokens), keeping the last Kq (0: only the K/V rows are produced).  Returns (x_next, qkv)."""
-        m = self.m
-        cfg = m.config
-        d, f = cfg.hidden_dim, cfg.ffn_dim
-        dev = x.device
-        mp = self._layer_maps(B, I, max(Kq, 1), p0, I_full)
-        ma, mt = mp['all'].to(dev), mp['tail'].to(dev)
-        na, nt = mp['all'].ntiles, mp['tail'].ntiles
-        wqkv, wo = m.pT(f'blk.{l}.wqkv'), m.pT(f'blk.{l}.wo')
-        w1, b1, w2, b2 = m.pT(f'blk.{l}.w1'), m.p(f'blk.{l}.b1'), m.pT(f'blk.{l}.w2'), m.p(f'blk.{l}.b2')
-        g1, g2 = m.p(f'blk.{l}.norm1'), m.p(f'blk.{l}.norm2')
-        rstd1 = torch.empty(B * I, device=dev)
-        K.rmsnorm_fwd(x, d, B * I, d, rstd1, eps=RMS_EPS)
-        qkv = torch.empty(B * I, 3 * d, device=dev)
-        # K/V for every row (weight cols d..3d of each group's [d, 3d] bank), Q for the kept rows
-        K.gemm(OT_GEMM_NT, x, d, d, ma['rows'][0], (wqkv, d * d), 3 * d * d, d, 2 * d, ma['tile_group'], na,
-               (qkv, d), 3 * d, ma['rows'][0], a_xform=OT_AX_RMSNORM, rstd=rstd1, gamma=g1, m_rows=mp['all'].nrows)
-        if Kq == 0:
-            return None, qkv
-        K.gemm(OT_GEMM_NT, x, d, d, mt['rows'][0], wqkv, 3 * d * d, d, d, mt['tile_group'], nt, qkv, 3 * d,
-               mt['rows'][0], a_xform=OT_AX_RMSNORM, rstd=rstd1, gamma=g1, m_rows=mp['tail'].nrows)
-        o = attn(qkv)                                                   # [B*Kq, d]
-        x1 = torch.empty(B * Kq, d, device=dev)
-        K.gemm(OT_GEMM_NT, o, d, d, mt['rows'][1], wo, 0, d, d, mt['tile_group'], nt, x1, d, mt['rows'][1],
-               epi=OT_EPI_RESIDUAL, res=x, ldres=d, res_tok=1, tail=(Kq, I), m_rows=mp['tail'].nrows)
-        rstd2 = torch.empty(B * Kq, device=dev)
-        K.rmsnorm_fwd(x1, d, B * Kq, d, rstd2, eps=RMS_EPS)
-        u = torch.empty(B * Kq, f, device=dev)
-        K.gemm(OT_GEMM_NT, x1, d, d, mt['rows'][1], w1, d * f, d, f, mt['tile_group'], nt, u, f, mt['rows'][1],
-               a_xform=OT_AX_RMSNORM, rstd=rstd2, gamma=g2, bias=b1, bias_gstride=f, epi=OT_EPI_BIAS,
-               m_rows=mp['tail'].nrows)
-        x2 = torch.empty(B * Kq, d, device=dev)
-        K.gemm(OT_GEMM_NT, u, f, f, mt['rows'][1], w2, f * d, f, d, mt['tile_group'], nt, x2, d, mt['rows'][1],
-               a_xform=OT_AX_GELU, bias=b2, bias_gstride=d, epi=OT_EPI_BIAS | OT_EPI_RESIDUAL, res=x1, ldres=d,
-               res_tok=0, tail=(Kq, I), m_rows=mp['tail'].nrows)
-        return x2, qkv
 
     # ------------------------------------------------------------------ stage I
     @torch.no_grad()
@@ -145,28 +82,18 @@ class OneTransServer:
         from .model import _Tokenize
         m = self.m
         cfg = m.config
-        d, H = cfg.hidden_dim, cfg.num_heads
-        hd = d // H
         if not seq_features:
             raise ValueError('encode_requests: no sequence features')
         plan = m._plan({}, seq_features)
-        R, L0, L_S = plan['B'], plan['L0'], plan['L_S']
-        x0 = _Tokenize.apply(m.flat, m, plan)                             # NS rows zero (no NS features)
-        x = x0.view(R, L0, d)[:, :L_S].reshape(R * L_S, d)
+        R, L_S = plan['B'], plan['L_S']
+        x = s_rows(_Tokenize.apply(m.flat, m, plan), plan)                # NS rows zero (no NS features)
         layers = []
         for l, e in enumerate(self.schedule(L_S)):
             s, kS = e['s'], e['kS']
             if s == 0:
                 layers.append({'Ic': 0, 'kv': None})
                 continue
-
-            def attn(qkv, s=s, kS=kS):
-                o = torch.empty(R * kS, d, device=qkv.device)
-                lse = torch.empty(R * H * kS, device=qkv.device)
-                K.attn_fwd(qkv, 3 * d, R, H, s, kS, hd, o, lse)           # S queries see S keys only
-                return o
-
-            x, qkv = self._block(l, x, R, s, kS, 0, e['I'], attn)
+            x, qkv, _ = span_forward(m, l, x, R, s, kS, 0, e['I'], cached=False)     # S queries see S keys only
             layers.append({'Ic': s, 'kv': qkv})
         present = [n for n in cfg.feature_config['sequence_features'] if n in seq_features]
         last_time = plan['last_time'].clone() if m.time_fusion else None
@@ -196,8 +123,7 @@ class OneTransServer:
         from .model import _Tokenize
         m = self.m
         cfg = m.config
-        d, H = cfg.hidden_dim, cfg.num_heads
-        hd = d // H
+        d = cfg.hidden_dim
         seqs = cfg.feature_config['sequence_features']
         if m.time_fusion:
             if seq_name not in seqs or seq_name not in cache.present:
@@ -219,9 +145,8 @@ class OneTransServer:
             raise ValueError(f'extend_requests: {plan["B"]} rows of new events for {R} cached requests')
         dL = plan['L_S']
         # 'time': the new events among themselves are ordered by the same kernel (one sequence)
-        x0 = _Tokenize.apply(m.flat, m, plan)                             # [R*(dL+L_NS), d], no [SEP]
+        x = s_rows(_Tokenize.apply(m.flat, m, plan), plan)                # [R*dL, d], no [SEP]
         last_time = plan['last_time'].clone() if m.time_fusion else None
-        x = x0.view(R, dL + cfg.num_ns_tokens, d)[:, :dL].reshape(R * dL, d)
         new = self.schedule(cache.L_S + dL)
         req = torch.arange(R, dtype=torch.int32, device=x.device)
         layers = []
@@ -229,14 +154,8 @@ class OneTransServer:
             Ic = e_old['s']
             lay = cache.layers[l]
             keep = e_new['kS'] - e_old['kS']                              # new S rows kept by this layer
-
-            def attn(qkv, Ic=Ic, lay=lay):
-                o = torch.empty(R * dL, d, device=qkv.device)
-                kv = (lay['kv'], d) if Ic > 0 else None
-                K.attn_fwd_cached(qkv, 3 * d, kv, 3 * d, req, R, H, Ic, dL, dL, hd, o)
-                return o
-
-            x, qkv = self._block(l, x, R, dL, dL if keep == dL else 0, Ic, e_new['I'], attn)
+            x, qkv, _ = span_forward(m, l, x, R, dL, dL if keep == dL else 0, Ic, e_new['I'], cached=True,
+                                     kv=lay['kv'] if Ic > 0 else None, req=req, R=R)
             kv = qkv if Ic == 0 else torch.cat([lay['kv'].view(R, Ic, 3 * d), qkv.view(R, dL, 3 * d)], 1)
             layers.append({'Ic': Ic + dL, 'kv': kv.reshape(R * (Ic + dL), 3 * d)})
         return RequestCache(R, cache.L_S + dL, layers, cache.present, last_time)
@@ -274,35 +193,18 @@ class OneTransServer:
         heads: (probs [T, C], req as device int32 [C])."""
         from .model import _Head, _Tokenize
         m = self.m
-        cfg = m.config
-        d, H = cfg.hidden_dim, cfg.num_heads
-        hd = d // H
-        dev = m.device
         plan = m._plan(non_seq_features, {})
         C = plan['B']
-        req = torch.as_tensor(req)
-        if req.numel() != C:
-            raise ValueError(f'{who}: {req.numel()} request indices for {C} candidates')
-        # the cached-attention kernel indexes the K/V cache with req unchecked: validate before launch
-        # (host indices directly; device indices with one min/max read-back)
-        lo, hi = (int(v) for v in torch.aminmax(req.reshape(-1).to(torch.int64)))
-        if lo < 0 or hi >= cache.R:
-            raise ValueError(f'{who}: request index out of range [0, {cache.R}) (min {lo}, max {hi})')
-        req = req.to(dev, torch.int32).contiguous()
+        check_req(who, req, cache.R, C, ordered=False)
+        req = torch.as_tensor(req).to(m.device, torch.int32).contiguous()
         x = _Tokenize.apply(m.flat, m, plan)                              # [C*L_NS, d]: NS tokens only
         for l, e in enumerate(self.schedule(cache.L_S)):
             s, n, kN = e['s'], e['n'], e['kN']
             lay = cache.layers[l]
             if lay['Ic'] != s:
                 raise OneTransHipError(f'{who}: request cache does not match the schedule')
-
-            def attn(qkv, lay=lay, s=s, n=n, kN=kN):
-                o = torch.empty(C * kN, d, device=dev)
-                kv = (lay['kv'], d) if s > 0 else None
-                K.attn_fwd_cached(qkv, 3 * d, kv, 3 * d, req, C, H, s, n, kN, hd, o)
-                return o
-
-            x, _ = self._block(l, x, C, n, kN, s, e['I'], attn)
+            x, _, _ = span_forward(m, l, x, C, n, kN, s, e['I'], cached=True, kv=lay['kv'] if s > 0 else None,
+                                   req=req, R=cache.R)
         probs, _ = _Head.apply(m.flat, x, m)                               # [T, C]
         return probs, req
 

@@ -17,7 +17,8 @@ from recommend_amd.data import expand_requests, make_request_batch
 from recommend_amd.model import OneTransModel, keras_bce_loss
 from recommend_amd.params import init_params
 from recommend_amd.request_train import n_span_seed
-from recommend_amd.serving import request_schedule
+from recommend_amd.serving import OneTransServer
+from recommend_amd.span_block import request_schedule
 from recommend_amd.trainer import OneTransTrainer, stack_labels
 from oracle import keras_math as km
 from oracle import onetrans_ref as R
@@ -161,6 +162,21 @@ def test_one_candidate_per_request(dev):
     got = run_requests(model, cfg, batch, dev, training=False)
     compare(got, run_expanded(model, cfg, batch, dev), 2, 'c=1 vs expanded')
     compare(got, oracle_side(P, cfg, batch), 1, 'c=1 vs oracle', oracle_b=True)
+
+
+@pytest.mark.parametrize('fusion', ['sep', 'time'])
+def test_evaluation_forward_equals_cached_serving(dev, fusion):
+    """The evaluation forward of the request path and cached serving run one span block
+    (recommend_amd/span_block.py): the same launches on the same operands, so the same bits — over a layer with
+    kept S rows, one with S rows but none kept, one without S rows, and a request without candidates."""
+    cfg = small(fusion=fusion)
+    _, model, (ns, seq, _, req) = case(cfg, dev)
+    nsd, sqd, reqd = t_(ns, dev), t_(seq, dev), torch.from_numpy(req).to(dev)
+    with torch.no_grad():
+        probs = model.forward_probs_requests(nsd, sqd, reqd, training=False)
+        srv = OneTransServer(model)
+        scores = srv.score(srv.encode_requests(sqd), reqd, nsd)
+    assert torch.equal(probs, torch.stack([scores[t].reshape(-1) for t in cfg.tasks]))
 
 
 def request_masks(cfg, L_S, req):

@@ -20,7 +20,7 @@ from recommend_amd import kernels as K
 from recommend_amd.config import workload_config
 from recommend_amd.data import expand_requests, make_request_batch
 from recommend_amd.model import OneTransModel
-from recommend_amd.serving import request_schedule
+from recommend_amd.span_block import request_schedule
 from recommend_amd.trainer import OneTransTrainer, stack_labels
 
 ap = argparse.ArgumentParser()
@@ -113,7 +113,7 @@ for label, e in (('first_layer', sched[0]), ('last_layer', sched[-1])):
         req_start = torch.arange(R + 1, dtype=torch.int32, device=dev) * c
         out, lse = torch.empty(C * Kq, d, device=dev), torch.empty(C * H * Kq, device=dev)
         dqkv, dkv = torch.zeros(C * n, 3 * d, device=dev), torch.zeros(R * Ic, 3 * d, device=dev)
-        fwd = lambda: K.attn_fwd_cached_lse(qkv, 3 * d, (kv, d), 3 * d, req, C, H, Ic, n, Kq, hd, out, lse)
+        fwd = lambda: K.attn_fwd_cached(qkv, 3 * d, (kv, d), 3 * d, req, C, H, Ic, n, Kq, hd, out, lse)
         bwd = lambda: K.attn_bwd_cached(qkv, 3 * d, (kv, d), 3 * d, req_start, R, C, H, Ic, n, Kq, hd, out, dout, lse,
                                         dqkv, (dkv, d))
         for name, fn in (('fwd_cached_lse', fwd), ('bwd_cached', bwd)):
