@@ -292,6 +292,38 @@ int ot_mixed_gemm_rms_img(int mode, const float* A, int64_t lda, int K, const in
                           const int32_t* tail_pos, const ot_rms_epilogue* rms, const uint16_t* b_image,
                           int image_ntn, int image_tn0, int precision, void* stream);
 
+/* The fused FFN forward of the split mode at hidden width 128 (model.py:154-161, 198):
+ *   u = rstd * (x1 @ (gamma W1[g])) + b1[g],  x2 = x1 + drop(gelu(u) @ W2[g] + b2[g])  [, rstd_out = rstd(x2)]
+ * in one launch: a row tile's u stays in the accumulators between the two products (scaled fp16 pair arithmetic, as
+ * the OT_AX_RMSNORM / OT_AX_GELU plane GEMMs with pair-form images), so u is neither read back nor, without u_out,
+ * written.  u (when written) equals the FFN1 launch's bit for bit; x2 differs from the FFN2 launch's by rounding (a
+ * row scale per 128 columns of u instead of one per row, another k order).  The dropout mask, bias, residual and
+ * rstd arithmetic are the FFN2 epilogue's. */
+typedef struct ot_ffn_fused_args {
+  size_t struct_size;                                  /* sizeof(ot_ffn_fused_args): any other value is refused */
+  const float* x1; int64_t ldx1;                       /* FFN input and residual rows, 128 floats each */
+  const int32_t* rows;                                 /* [ntiles * 128] row of x1 / u / x2 per tile row, -1 = none;
+                                                          NULL = identity */
+  const int32_t* tile_group; int ntiles;               /* weight group per tile (NULL: group 0) */
+  const float* rstd;                                   /* norm2's rstd per x1 row */
+  const uint16_t* w1_image; int w1_groups;             /* ot_split_images pair images: W1 forward (gamma folded, f / 128 */
+  const uint16_t* w2_image; int w2_groups;             /* column tiles of 8 units per group), W2 forward (f / 16 units) */
+  const float* b1; int64_t b1_gstride;
+  const float* b2; int64_t b2_gstride;
+  int f;                                               /* FFN width: a multiple of 128, at most 1024 */
+  float* u_out; int64_t ldu;                           /* optional (training): u */
+  float* u_amax;                                       /* optional: *u_amax = max(*u_amax, max |u|) as amax_out */
+  float* x2; int64_t ldx2;
+  float* rstd_out; float eps;                          /* optional: the next RMSNorm's rstd (OT_EPI_ROW_RSTD) */
+  uint32_t seed, site; float drop_rate;                /* dropout as ot_mixed_gemm's (0: none) */
+  int tail_K, tail_I; const int32_t* tail_pos;
+} ot_ffn_fused_args;
+int ot_ffn_fused_fwd(const ot_ffn_fused_args* args, void* stream);
+/* Whether the model's block forward takes ot_ffn_fused_fwd where its form applies (1, default) or the FFN1 and FFN2
+ * launches (0).  Process-wide; on = -1 only queries; returns the previous setting.  The library only keeps the
+ * setting: the host layer reads it. */
+int ot_ffn_fused(int on);
+
 /* ---- causal attention with a query tail (attention.hip) ----------------------------------
  * Replaces model.py:100-114 (einsum QK^T/sqrt(hd), band_part mask with -1e9, softmax, einsum PV)
  * and the pyramid gather of queries model.py:356/371 (only the last K of I queries computed).

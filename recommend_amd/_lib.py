@@ -51,6 +51,18 @@ class RmsEpilogue(ctypes.Structure):
                 ('a_rowmax', c_void_p), ('a_rowmax_n', c_int),
                 ('amax_out', c_void_p), ('rowabs_out', c_void_p), ('rowabs_n', c_int)]
 
+class FfnFusedArgs(ctypes.Structure):
+    """``ot_ffn_fused_args`` (include/onetrans_hip.h)."""
+    _fields_ = [('struct_size', c_size_t), ('x1', c_void_p), ('ldx1', c_int64), ('rows', c_void_p),
+                ('tile_group', c_void_p), ('ntiles', c_int), ('rstd', c_void_p),
+                ('w1_image', c_void_p), ('w1_groups', c_int), ('w2_image', c_void_p), ('w2_groups', c_int),
+                ('b1', c_void_p), ('b1_gstride', c_int64), ('b2', c_void_p), ('b2_gstride', c_int64),
+                ('f', c_int), ('u_out', c_void_p), ('ldu', c_int64), ('u_amax', c_void_p),
+                ('x2', c_void_p), ('ldx2', c_int64), ('rstd_out', c_void_p), ('eps', c_float),
+                ('seed', c_uint32), ('site', c_uint32), ('drop_rate', c_float),
+                ('tail_K', c_int), ('tail_I', c_int), ('tail_pos', c_void_p)]
+
+
 class SeqTime(ctypes.Structure):
     """``ot_seq_time`` (include/onetrans_hip.h): one sequence's times and its segment of the row map."""
     _fields_ = [('times', c_void_p), ('stride_b', c_int64), ('L', ctypes.c_int32), ('map_off', ctypes.c_int32)]
@@ -105,6 +117,8 @@ SIGNATURES = {
     'ot_plane_rowmeta': (c_int, [c_int]),
     'ot_plane_panel': (c_int, [c_int]),
     'ot_plane_panel_launches': (c_int, []),
+    'ot_ffn_fused_fwd': (c_int, [P, P]),
+    'ot_ffn_fused': (c_int, [c_int]),
     'ot_split_images': (c_int, [P, P, c_int, I64, P, c_int, P]),
     'ot_attn_fwd': (c_int, [P, I64, c_int, c_int, c_int, c_int, P, c_int, P, P, c_int, P]),
     'ot_attn_fwd_fp8_workspace_size': (c_size_t, [c_int, c_int, c_int, c_int]),

@@ -108,7 +108,9 @@ __device__ __forceinline__ float row32_sum(float v) {
 // tile held by 2x2 waves): wave 2 r + sub holds rows 64 r + 32 m, cols 32 nb in acc[4 m + nb]; LAYOUT 3 (128-column
 // quarter `sub` of a 512-column tile): wave `sub` holds all 128 rows, rows 32 m / cols 32 nb in acc[4 m + nb];
 // LAYOUT 4 (128-column half `sub` of a 256 x 256 tile's row half, the epilogue run by that row half's four waves
-// with thread ids `tid` 0..255): wave 2 sub + j holds all 128 rows x columns 64 j + 32 nb in acc[2 m + nb].
+// with thread ids `tid` 0..255): wave 2 sub + j holds all 128 rows x columns 64 j + 32 nb in acc[2 m + nb];
+// LAYOUT 5 (4x1 waves, transposed accumulators: the fused FFN, gemm_ffn.hip): lane li holds row 32 wave + li,
+// acc[nb][r] = column 32 nb + (r & 3) + 8 (r >> 2) + 4 h.
 // ROWSCALE: multiply row r by
 // a_rstd[in_rows[r]] first (the plane GEMM's RMSNorm prologue, folded into the weights).
 __device__ __forceinline__ void store_out4(float* dst, f32x4 v) {
@@ -178,7 +180,7 @@ __device__ __forceinline__ void gemm_vec_epilogue(const GemmArgs& p, const f32x1
       for (int i = 0; i < 8; ++i) {
         const int lr = rb + 8 * i;                      // local row of the half: tile row below
         const int64_t gr = (int64_t)tm * GT + (LAYOUT == 0 ? (lr >> 5) * 64 + 32 * hf + (lr & 31) : 64 * hf + lr);
-        if (LAYOUT == 1 && rmeta) {                     // parked by the kernel's prologue
+        if ((LAYOUT == 1 || LAYOUT == 5) && rmeta) {    // parked by the kernel's prologue
           orow[i] = rmeta[64 * hf + lr];
           if (ROWSCALE) rsc[i] = __int_as_float(rmeta[GT + 64 * hf + lr]);
           continue;
@@ -202,6 +204,15 @@ __device__ __forceinline__ void gemm_vec_epilogue(const GemmArgs& p, const f32x1
 #pragma unroll
             for (int r = 0; r < 16; ++r)
               ct[((wave & 1) * 32 + (r & 3) + 8 * (r >> 2) + 4 * h) * CLD + 32 * nb + li] = acc[nb][r];
+        }
+      } else if (LAYOUT == 5) {                         // LAYOUT 5: lane = row, four consecutive columns per store
+        if ((wave >> 1) == hf) {
+#pragma unroll
+          for (int nb = 0; nb < 4; ++nb)
+#pragma unroll
+            for (int qd = 0; qd < 4; ++qd)
+              *reinterpret_cast<f32x4*>(ct + ((wave & 1) * 32 + li) * CLD + 32 * nb + 8 * qd + 4 * h) =
+                  f32x4{acc[nb][4 * qd], acc[nb][4 * qd + 1], acc[nb][4 * qd + 2], acc[nb][4 * qd + 3]};
         }
       } else if (LAYOUT == 4) {                         // LAYOUT 4: waves 2 sub, 2 sub + 1 (64 columns each)
         if ((wave >> 1) == sub) {

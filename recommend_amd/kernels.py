@@ -372,6 +372,39 @@ def plane_panel_launches() -> int:
     return _lib.size('ot_plane_panel_launches')
 
 
+def ffn_fused(on: int = -1) -> int:
+    """ot_ffn_fused: whether the block forward takes the fused FFN kernel where its form applies (split mode, hidden
+    width 128, pair-form W1 / W2 forward images, ffn width a multiple of 128 up to ``FFN_FUSED_MAX_F``) — 1 (default)
+    or 0: the FFN1 and FFN2 launches — or query (-1); returns the previous setting."""
+    return _lib.size('ot_ffn_fused', int(on))
+
+
+FFN_FUSED_MAX_F = 1024
+
+
+def ffn_fused_fwd(x1: Ptrish, ldx1: int, rows: Ptrish, tile_group: Ptrish, ntiles: int, rstd: Ptrish, w1_image,
+                  w1_groups: int, w2_image, w2_groups: int, b1: Ptrish, b1_gstride: int, b2: Ptrish, b2_gstride: int,
+                  f: int, x2: Ptrish, ldx2: int, *, u_out: Ptrish = None, ldu: int = 0, u_amax: Ptrish = None,
+                  rstd_out: Ptrish = None, eps: float = 1e-6, seed: int = 0, site: int = 0, drop: float = 0.0,
+                  tail: Tuple[int, int] = (1, 1), m_rows: int = 0) -> None:
+    """ot_ffn_fused_fwd: x2 = x1 + drop(gelu(rstd * (x1 @ gamma W1[g]) + b1[g]) @ W2[g] + b2[g]) for rows of 128
+    floats in one launch (split mode; ``w1_image`` / ``w2_image``: the pair-form forward images as ``(tensor,
+    element offset)``); ``u_out`` also receives the pre-activation (bit for bit the FFN1 launch's), ``u_amax`` its
+    max |u|, ``rstd_out`` the rstd of the x2 rows."""
+    a = _lib.FfnFusedArgs(ctypes.sizeof(_lib.FfnFusedArgs), ptr(x1), ldx1, ptr(rows), ptr(tile_group), ntiles,
+                          ptr(rstd), ptr(w1_image), int(w1_groups), ptr(w2_image), int(w2_groups), ptr(b1),
+                          b1_gstride, ptr(b2), b2_gstride, f, ptr(u_out), ldu, ptr(u_amax), ptr(x2), ldx2,
+                          ptr(rstd_out), float(eps), seed & 0xFFFFFFFF, site, float(drop), tail[0], tail[1],
+                          _sel(tail))
+    ev = _probe.begin() if _probe is not None else None
+    call('ot_ffn_fused_fwd', ctypes.byref(a), stream())
+    if ev is not None:
+        M = m_rows or ntiles * 128
+        _probe.end('mixed_gemm', 2.0 * M * 128 * f * 2, ev, f'ffn_fused M{M} f{f} u{int(u_out is not None)}',
+                   4.0 * M * 128 * 3 + 4.0 * M * f * (u_out is not None)
+                   + 4.0 * M * (1 + (rstd_out is not None)), 3)
+
+
 def split_images(base, desc_dev, ndesc, total_units, img) -> None:
     call('ot_split_images', ptr(base), ptr(desc_dev), ndesc, total_units, ptr(img), _prec(), stream())
 

@@ -175,9 +175,10 @@ def _attn_qpos(cfg, pos):
     return None if getattr(cfg, 'pyramid_select', 'tail') == 'tail' else pos
 
 
-def _block_forward(m, l, x, I, Kq, seed, training, rstd_in=None, select=False, need_out=True):
+def _block_forward(m, l, x, I, Kq, seed, training, rstd_in=None, select=False, need_out=True, need_u=True):
     """The block's forward kernels (``_Block.forward``; also the backward's recompute with
     ``need_out=False``, which stops after FFN1: the backward needs u, not the block output).
+    ``need_u=False`` (no backward will read this call's u): the fused FFN forward does not write it (saved u None).
     Returns (x2, rstd_out, saved, pos, inv, rate); saved = (x, rstd1, qkv, o, lse, x1, rstd2, u, h, xn1, x1n);
     h = the stored bf16 gelu(u), xn1 / x1n = the bf16 normalised QKV / FFN1 inputs (bf16 mode) or None."""
     cfg = m.config
@@ -313,6 +314,20 @@ def _block_forward(m, l, x, I, Kq, seed, training, rstd_in=None, select=False, n
     pair_w2 = K.matmul_mode() == 'split' and w2img is not None and (f'blk.{l}.w2', 'fwd') in m.layout.pair_images
     assert not pair_w2 or (h is None and m.bimg(f'blk.{l}.w1') is not None and f % TILE == 0), \
         'the pair-form W2 image needs the FFN1 plane GEMM to write the row maxima of u'
+    # split mode, d == 128, the block output wanted: FFN1 -> GELU -> FFN2 in one launch (ot_ffn_fused_fwd: u stays in
+    # the accumulators, no row maxima round trip); the recompute (need_out False) wants u only: the FFN1 launch
+    if (pair_w2 and need_out and d == TILE and f <= K.FFN_FUSED_MAX_F and x1_16 is None and K.ffn_fused()):
+        if not need_u:
+            u = None
+        x2 = torch.empty(B * Kq, d, device=dev)
+        rstd_out = torch.empty(B * Kq, device=dev) if fuse else None
+        K.ffn_fused_fwd(x1, d, mt['rows'][1], mt['tile_group'], nt, rstd2, m.bimg(f'blk.{l}.w1')[0],
+                        m.layout.images[(f'blk.{l}.w1', 'fwd')][1], w2img[0],
+                        m.layout.images[(f'blk.{l}.w2', 'fwd')][1], b1, f, b2, d, f, x2, d, u_out=u, ldu=f,
+                        u_amax=m.amax_slot(l, 1) if training else None, rstd_out=rstd_out, eps=RMS_EPS, seed=seed,
+                        site=2 * l + 1, drop=rate, tail=tail, m_rows=maps['tail'].nrows)
+        saved = (x, rstd1, qkv, o, lse, x1, rstd2, u, None, xn1, None)
+        return x2, rstd_out, saved, pos, inv, rate
     umax = torch.empty(B * Kq, f // TILE, device=dev) if pair_w2 else None
     if h is not None:
         K.gemm_rms(OT_GEMM_NT, x1 if x1_16 is None else x1_16, d, d, mt['rows'][1], w1, d * f, d, f,
@@ -375,7 +390,11 @@ class _Block(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, flat, x, m, l, I, Kq, seed, training, rstd_in=None, select=False):
-        x2, rstd_out, saved, pos, inv, rate = _block_forward(m, l, x, I, Kq, seed, training, rstd_in, select)
+        # u is read by a backward only: with the recompute (which forms it again) or no input that needs a gradient
+        # (inference) this forward need not write it
+        x2, rstd_out, saved, pos, inv, rate = _block_forward(
+            m, l, x, I, Kq, seed, training, rstd_in, select,
+            need_u=not m.recompute and any(ctx.needs_input_grad))
         if m.recompute:
             # activation recompute: keep the block input (and its rstd); the backward re-runs the
             # forward kernels up to FFN1 (dropout masks and pyramid keeps are deterministic)
