@@ -478,7 +478,9 @@ int ot_dropout_apply(const float* src, int64_t lds, float* dst, int64_t ldd, int
                      const int32_t* tail_pos, void* stream);
 /* ot_dropout_apply that also reports the output's magnitude for fp16-pair consumers: amax (optional, one float the
  * caller zeroes) = max(*amax, max |out|) (atomic, order-independent); rowmax (optional, [rows][rowmax_n], rowmax_n =
- * ceil(d / 256), d / 4 a power of two or a multiple of 64) = max |out| of each row's 256-column parts */
+ * ceil(d / 256)) = max |out| of each row's 256-column parts, only where ot_dropout_rowmax_supported(d) is 1 (d / 4 a
+ * power of two or a multiple of 64; elsewhere a rowmax is refused and ot_rows_absmax stands in) */
+int ot_dropout_rowmax_supported(int d);
 int ot_dropout_apply_ex(const float* src, int64_t lds, float* dst, int64_t ldd, int64_t rows, int d,
                         uint32_t seed, uint32_t site, float drop_rate, int tail_K, int tail_I,
                         const int32_t* tail_pos, float* amax, float* rowmax, int rowmax_n, void* stream);

@@ -151,6 +151,7 @@ SIGNATURES = {
     'ot_dropout_apply': (c_int, [P, I64, P, I64, I64, c_int, c_uint32, c_uint32, c_float, c_int, c_int, P, P]),
     'ot_dropout_apply_bf16': (c_int, [P, I64, P, I64, I64, c_int, c_uint32, c_uint32, c_float, c_int, c_int, P, P]),
     'ot_rows_absmax': (c_int, [P, I64, I64, c_int, P, c_int, P]),
+    'ot_dropout_rowmax_supported': (c_int, [c_int]),
     'ot_dropout_apply_ex': (c_int, [P, I64, P, I64, I64, c_int, c_uint32, c_uint32, c_float, c_int, c_int, P, P, P,
                                     c_int, P]),
     'ot_rows_colsum_workspace_size': (c_size_t, [I64, c_int]),

@@ -335,13 +335,19 @@ extern "C" int ot_dropout_apply(const float* src, int64_t lds, float* dst, int64
   return OT_OK;
 }
 
+// dropout_apply_kernel's row maxima reduce over groups of min(d / 4, 64) lanes: whole rows (or 256-column parts) only
+// when d / 4 is a power of two or a multiple of 64
+extern "C" int ot_dropout_rowmax_supported(int d) {
+  const int q = d / 4;
+  return d > 0 && d % 4 == 0 && (q % 64 == 0 || (q & (q - 1)) == 0);
+}
+
 extern "C" int ot_dropout_apply_ex(const float* src, int64_t lds, float* dst, int64_t ldd, int64_t rows, int d,
                                    uint32_t seed, uint32_t site, float drop_rate, int tail_K, int tail_I,
                                    const int32_t* tail_pos, float* amax, float* rowmax, int rowmax_n, void* stream) {
   OT_REQUIRE(src && dst && d % 4 == 0 && lds % 4 == 0 && ldd % 4 == 0, "ot_dropout_apply_ex: bad args");
   OT_REQUIRE(tail_K > 0 && tail_I >= tail_K, "ot_dropout_apply_ex: bad tail map");
-  const int q = d / 4;
-  OT_REQUIRE(!rowmax || (rowmax_n == (d + 255) / 256 && (q % 64 == 0 || (q & (q - 1)) == 0)),
+  OT_REQUIRE(!rowmax || (rowmax_n == (d + 255) / 256 && ot_dropout_rowmax_supported(d)),
              "ot_dropout_apply_ex: rowmax needs rowmax_n == ceil(d / 256) and d / 4 a power of two or a multiple of 64");
   if (rows == 0) return OT_OK;
   hipLaunchKernelGGL(dropout_apply_kernel<float>, dim3(ceil_div(ceil_div(rows * d / 4, DROPOUT_PASSES), 256)), dim3(256), 0, (hipStream_t)stream,

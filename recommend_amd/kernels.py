@@ -547,6 +547,11 @@ def dropout_apply(src, lds, dst, ldd, rows, d, seed, site, drop, tail, amax=None
         _probe.end('rowwise', 0.0, ev)
 
 
+def dropout_rowmax_supported(d: int) -> bool:
+    """ot_dropout_rowmax_supported: does ``dropout_apply`` report ``rowmax`` at this row width?"""
+    return bool(_lib.load().ot_dropout_rowmax_supported(d))
+
+
 def rows_absmax(x, ldx, rows, d, out) -> None:
     """ot_rows_absmax: out [rows][ceil(d / 256)] = each row's 256-column parts' max |x| (an fp16-pair GEMM's a_rowmax)."""
     ev = _probe.begin() if _probe is not None else None

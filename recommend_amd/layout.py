@@ -56,7 +56,7 @@ class FlatLayout:
     """Offsets of every dense bank inside the flat parameter buffer."""
 
     def __init__(self, cfg: OneTransConfig, f_ns: int, pair_dgrad: bool = False):
-        self.f_ns = f_ns
+        self.f_ns, self.pair_dgrad = f_ns, pair_dgrad
         self.f_pad = max(4, round_up(f_ns, 4))
         self.shapes = dense_param_shapes(cfg, self.f_pad)
         self.offsets: Dict[str, int] = {}

@@ -175,10 +175,43 @@ def _attn_qpos(cfg, pos):
     return None if getattr(cfg, 'pyramid_select', 'tail') == 'tail' else pos
 
 
-def _block_forward(m, l, x, I, Kq, seed, training, rstd_in=None, select=False, need_out=True, need_u=True):
+class PairBounds:
+    """Magnitude bounds of the fp16-pair weight gradients' operands (split mode, ot_mixed_gemm_wgrad_ex) for one
+    forward and its backward: a zeroed float per layer and slot, into which the producing kernel folds max |output|
+    (an atomic max: the recompute's second fold of the same values changes nothing).  ``out`` is the producer's
+    view; ``get`` the consumer's, None unless a producer took it — no bound, like no object: the exact split."""
+    SLOTS = ('o', 'u', 'dy2', 'du', 'dyo', 'dqkv')     # |O|, |U|, |dY2|, |dU|, |dX1 masked|, |dQKV|
+
+    def __init__(self, layers: int, device):
+        self.t, self._taken = torch.zeros(layers, 8, device=device), {}
+
+    @classmethod
+    def begin(cls, layers: int, device, mode: str, pair_wgrad: bool) -> Optional['PairBounds']:
+        """For a forward in split mode with ONETRANS_PAIR_WGRAD on that a backward can follow; else None."""
+        return cls(layers, device) if mode == 'split' and pair_wgrad and torch.is_grad_enabled() else None
+
+    def out(self, l: int, name: str) -> torch.Tensor:
+        return self._taken.setdefault((l, name), self.t[l, self.SLOTS.index(name):][:1])
+
+    def get(self, l: int, name: str) -> Optional[torch.Tensor]:
+        return self._taken.get((l, name))
+
+
+def a_row_bounds(on: bool, x, ld: int, rows: int, n: int, reported=None) -> Dict:
+    """The GEMM arguments that hand an fp16-pair image (``on``: gemm_pair) its A rows' maxima: those x's producer
+    ``reported``, else one row-absmax pass over x [rows, n]."""
+    if on and reported is None:
+        reported = torch.empty(rows, (n + 255) // 256, device=x.device)
+        K.rows_absmax(x, ld, rows, n, reported)
+    return dict(a_rowmax=reported, a_rowmax_n=reported.shape[1]) if on else {}
+
+
+def _block_forward(m, l, x, I, Kq, seed, training, rstd_in=None, select=False, need_out=True, need_u=True,
+                   bounds=None):
     """The block's forward kernels (``_Block.forward``; also the backward's recompute with
     ``need_out=False``, which stops after FFN1: the backward needs u, not the block output).
     ``need_u=False`` (no backward will read this call's u): the fused FFN forward does not write it (saved u None).
+    ``bounds``: this forward's PairBounds or None.
     Returns (x2, rstd_out, saved, pos, inv, rate); saved = (x, rstd1, qkv, o, lse, x1, rstd2, u, h, xn1, x1n);
     h = the stored bf16 gelu(u), xn1 / x1n = the bf16 normalised QKV / FFN1 inputs (bf16 mode) or None."""
     cfg = m.config
@@ -264,17 +297,14 @@ def _block_forward(m, l, x, I, Kq, seed, training, rstd_in=None, select=False, n
     qp_f = _attn_qpos(cfg, pos)
     qkv16 = (torch.empty(B * I, 3 * d, dtype=torch.int16, device=dev)
              if m.attn_fp8 and training and K.attn_bwd_bf16_supported(I, Kq, hd, qp_f) else None)
-    am_o = (m.amax_slot(l, 0) if training and not m.attn_fp8 and K.attn_amax_supported(I, Kq, hd, qp_f) else None)
-    # the Wo forward on the fp16 pair (pair-form Wo image): O's row maxima, per head, from the slice forward (else
-    # the row-absmax pass)
+    out = (lambda name: bounds.out(l, name)) if bounds is not None else (lambda name: None)
+    # the Wo forward on the fp16 pair (pair-form Wo image): O's row maxima, per head, and |O| from the slice forward
     pwo_f = m.gemm_pair(f'blk.{l}.wo', 'fwd')
-    o_fast = pwo_f and not m.attn_fp8 and K.attn_amax_supported(I, Kq, hd, qp_f)
-    rm_o = torch.empty(B * Kq, H, device=dev) if o_fast else None
-    K.attn_fwd(qkv, 3 * d, B, H, I, Kq, hd, o, lse, qpos=qp_f, fp8=m.attn_fp8,
-               dequant=m.attn_fp8 and training, fp8_terms=m.fp8_terms, deq16=qkv16, amax=am_o, rowmax=rm_o)
-    if pwo_f and rm_o is None:
-        K.rows_absmax(o, d, B * Kq, d, rm_o := torch.empty(B * Kq, (d + 255) // 256, device=dev))
-    pa_o = dict(a_rowmax=rm_o, a_rowmax_n=rm_o.shape[1]) if pwo_f else {}
+    o_rep = not m.attn_fp8 and K.attn_amax_supported(I, Kq, hd, qp_f)
+    rm_o = torch.empty(B * Kq, H, device=dev) if pwo_f and o_rep else None
+    K.attn_fwd(qkv, 3 * d, B, H, I, Kq, hd, o, lse, qpos=qp_f, fp8=m.attn_fp8, dequant=m.attn_fp8 and training,
+               fp8_terms=m.fp8_terms, deq16=qkv16, amax=out('o') if o_rep else None, rowmax=rm_o)
+    pa_o = a_row_bounds(pwo_f, o, d, B * Kq, d, rm_o)
     if qkv16 is not None:
         qkv = qkv16
     # x1 = x[tail] + drop(o @ Wo)      (model.py:117, 193)
@@ -324,8 +354,8 @@ def _block_forward(m, l, x, I, Kq, seed, training, rstd_in=None, select=False, n
         K.ffn_fused_fwd(x1, d, mt['rows'][1], mt['tile_group'], nt, rstd2, m.bimg(f'blk.{l}.w1')[0],
                         m.layout.images[(f'blk.{l}.w1', 'fwd')][1], w2img[0],
                         m.layout.images[(f'blk.{l}.w2', 'fwd')][1], b1, f, b2, d, f, x2, d, u_out=u, ldu=f,
-                        u_amax=m.amax_slot(l, 1) if training else None, rstd_out=rstd_out, eps=RMS_EPS, seed=seed,
-                        site=2 * l + 1, drop=rate, tail=tail, m_rows=maps['tail'].nrows)
+                        u_amax=out('u'), rstd_out=rstd_out, eps=RMS_EPS, seed=seed, site=2 * l + 1, drop=rate,
+                        tail=tail, m_rows=maps['tail'].nrows)
         saved = (x, rstd1, qkv, o, lse, x1, rstd2, u, None, xn1, None)
         return x2, rstd_out, saved, pos, inv, rate
     umax = torch.empty(B * Kq, f // TILE, device=dev) if pair_w2 else None
@@ -342,7 +372,7 @@ def _block_forward(m, l, x, I, Kq, seed, training, rstd_in=None, select=False, n
                    nt, u, f, mt['rows'][1], a_xform=OT_AX_RMSNORM if x1_16 is None else OT_AX_BF16_RMSNORM,
                    rstd=rstd2, gamma=g2, bias=b1, bias_gstride=f, epi=OT_EPI_BIAS, m_rows=maps['tail'].nrows,
                    bimg=m.bimg(f'blk.{l}.w1'), rowmax_out=umax, rowmax_n=umax.shape[1],
-                   amax_out=m.amax_slot(l, 1) if training else None)   # |U| >= |gelu(U)|: the W2 wgrad's A bound
+                   amax_out=out('u'))                 # |U| >= |gelu(U)|: the W2 wgrad's A bound
     else:
         K.gemm(OT_GEMM_NT, x1 if x1_16 is None else x1_16, d, d, mt['rows'][1], w1, d * f, d, f, mt['tile_group'],
                nt, u, f, mt['rows'][1], a_xform=OT_AX_RMSNORM if x1_16 is None else OT_AX_BF16_RMSNORM, rstd=rstd2,
@@ -357,6 +387,7 @@ def _block_forward(m, l, x, I, Kq, seed, training, rstd_in=None, select=False, n
     x2 = torch.empty(B * Kq, d, device=dev)
     rstd_out = None
     a2, ax2 = (h, OT_AX_BF16) if h is not None else (u, OT_AX_GELU)
+    pa_u = a_row_bounds(pair_w2, u, f, B * Kq, f, umax)
     if fuse:
         rstd_out = torch.empty(B * Kq, device=dev)
         x2_16 = torch.empty(B * Kq, d, dtype=torch.int16, device=dev) if m.x16_on(d) and w2img is not None else None
@@ -364,14 +395,13 @@ def _block_forward(m, l, x, I, Kq, seed, training, rstd_in=None, select=False, n
                    mt['rows'][1], a_xform=ax2, bias=b2, bias_gstride=d,
                    epi=OT_EPI_BIAS | OT_EPI_RESIDUAL | dflag | OT_EPI_ROW_RSTD, res=x1, ldres=d, res_tok=0,
                    seed=seed, site=2 * l + 1, drop=rate, tail=tail, m_rows=maps['tail'].nrows,
-                   rstd_out=rstd_out, eps=RMS_EPS, bimg=w2img, c16_out=x2_16, ldc16=d,
-                   a_rowmax=umax, a_rowmax_n=umax.shape[1] if umax is not None else 0)
+                   rstd_out=rstd_out, eps=RMS_EPS, bimg=w2img, c16_out=x2_16, ldc16=d, **pa_u)
         m.put_x16(l + 1, x2, x2_16)
     elif umax is not None:
         K.gemm_rms(OT_GEMM_NT, a2, f, f, mt['rows'][1], w2, f * d, f, d, mt['tile_group'], nt, x2, d, mt['rows'][1],
                    a_xform=ax2, bias=b2, bias_gstride=d, epi=OT_EPI_BIAS | OT_EPI_RESIDUAL | dflag, res=x1,
                    ldres=d, res_tok=0, seed=seed, site=2 * l + 1, drop=rate, tail=tail,
-                   m_rows=maps['tail'].nrows, bimg=w2img, a_rowmax=umax, a_rowmax_n=umax.shape[1])
+                   m_rows=maps['tail'].nrows, bimg=w2img, **pa_u)
     else:
         K.gemm(OT_GEMM_NT, a2, f, f, mt['rows'][1], w2, f * d, f, d, mt['tile_group'], nt, x2, d, mt['rows'][1],
                a_xform=ax2, bias=b2, bias_gstride=d, epi=OT_EPI_BIAS | OT_EPI_RESIDUAL | dflag, res=x1,
@@ -389,11 +419,11 @@ class _Block(torch.autograd.Function):
     of the next: ``rstd_in``), and the FFN1 / QKV dgrad epilogues apply the norm backward."""
 
     @staticmethod
-    def forward(ctx, flat, x, m, l, I, Kq, seed, training, rstd_in=None, select=False):
+    def forward(ctx, flat, x, m, l, I, Kq, seed, training, rstd_in=None, select=False, bounds=None):
         # u is read by a backward only: with the recompute (which forms it again) or no input that needs a gradient
         # (inference) this forward need not write it
         x2, rstd_out, saved, pos, inv, rate = _block_forward(
-            m, l, x, I, Kq, seed, training, rstd_in, select,
+            m, l, x, I, Kq, seed, training, rstd_in, select, bounds=bounds,
             need_u=not m.recompute and any(ctx.needs_input_grad))
         if m.recompute:
             # activation recompute: keep the block input (and its rstd); the backward re-runs the
@@ -403,7 +433,7 @@ class _Block(torch.autograd.Function):
         else:
             ctx.save_for_backward(*saved)
         ctx.m, ctx.l, ctx.I, ctx.Kq, ctx.seed, ctx.rate = m, l, I, Kq, seed, rate
-        ctx.pos, ctx.inv = pos, inv
+        ctx.pos, ctx.inv, ctx.bounds = pos, inv, bounds
         if rstd_out is None:
             rstd_out = x2.new_empty(0)          # not fused: the next block computes its own rstd
         ctx.mark_non_differentiable(rstd_out)
@@ -418,12 +448,12 @@ class _Block(torch.autograd.Function):
     @staticmethod
     def _backward(ctx, dx2, _drstd=None):
         m, l, I, Kq, seed, rate = ctx.m, ctx.l, ctx.I, ctx.Kq, ctx.seed, ctx.rate
-        pos, inv = ctx.pos, ctx.inv
+        pos, inv, bounds = ctx.pos, ctx.inv, ctx.bounds
         if m.recompute:
             xin, rstd_in = ctx.saved_tensors
             training, select = ctx.fwd_args
             _, _, saved, pos, inv, _ = _block_forward(m, l, xin, I, Kq, seed, training, rstd_in, select,
-                                                      need_out=False)
+                                                      need_out=False, bounds=bounds)
             x, rstd1, qkv, o, lse, x1, rstd2, u, h, xn1, x1n = saved
         else:
             x, rstd1, qkv, o, lse, x1, rstd2, u, h, xn1, x1n = ctx.saved_tensors
@@ -445,28 +475,22 @@ class _Block(torch.autograd.Function):
         du_bf = (fused2 and h is not None and m.bimg(f'blk.{l}.w1', 'dgrad') is not None)
         # FFN branch: dY2 = mask(dx2) — in bf16 with the bf16 dU path (its two readers, the FFN2 dgrad's A and
         # the W2 weight gradient's D, round it to bf16; the latter then runs copy-staged)
-        # fp16-pair weight gradients (split mode): magnitude bounds of their operands, folded in by the producers
-        # (amax_slot; None = no bound, the exact split runs).  |U| from the FFN1 forward (its plane-GEMM epilogue, the
-        # pair-form W2 path), |O| from the slice attention forward
-        am = lambda i: m.amax_slot(l, i)
-        qp_b = _attn_qpos(cfg, pos)
-        b_u = am(1) if m.u_bound_ok(l) else None
-        b_o = am(0) if (am(0) is not None and not m.attn_fp8 and K.attn_amax_supported(I, Kq, hd, qp_b)) else None
-        b_dy2 = b_du = b_dyo = b_dq = None
+        # fp16-pair weight gradients (split mode): their operands' bounds (PairBounds; None = the exact split runs):
+        # |U| and |O| where this backward's own forward took them; ``keep`` goes with the side stream's reads (m.side)
+        out = (lambda name: bounds.out(l, name)) if bounds is not None else (lambda name: None)
+        b_o, b_u = (bounds.get(l, 'o'), bounds.get(l, 'u')) if bounds is not None else (None, None)
+        keep = (bounds.t,) if bounds is not None else ()
         # fp16-pair dgrads (pair-form dgrad images): the A rows' maxima, from the producers where they report them
         pw2, pw1, pwo = (m.dgrad_pair(f'blk.{l}.{w}') for w in ('w2', 'w1', 'wo'))
-        rm_dy2 = torch.empty(B * Kq, (d + 255) // 256, device=dev) if pw2 else None
+        dy2_rep = rate > 0 and not du_bf           # the float32 dropout reports |dY2|, and row maxima at some widths
+        b_dy2 = out('dy2') if dy2_rep else None
+        rm_dy2 = (torch.empty(B * Kq, (d + 255) // 256, device=dev)
+                  if dy2_rep and pw2 and K.dropout_rowmax_supported(d) else None)
+        dy2 = dx2
         if rate > 0:
             dy2 = torch.empty(B * Kq, d, device=dev, dtype=torch.int16 if du_bf else torch.float32)
-            b_dy2 = am(2) if not du_bf else None
-            K.dropout_apply(dx2, d, dy2, d, B * Kq, d, seed, 2 * l + 1, rate, tail, amax=b_dy2,
-                            rowmax=rm_dy2 if not du_bf else None)
-        else:
-            dy2 = dx2
-            if rm_dy2 is not None:
-                K.rows_absmax(dy2, d, B * Kq, d, rm_dy2)
-        pa2 = dict(a_rowmax=rm_dy2, a_rowmax_n=rm_dy2.shape[1]) if pw2 else {}
-        rm_du = torch.empty(B * Kq, (f + TILE - 1) // TILE, device=dev) if pw1 else None
+            K.dropout_apply(dx2, d, dy2, d, B * Kq, d, seed, 2 * l + 1, rate, tail, amax=b_dy2, rowmax=rm_dy2)
+        pa2 = a_row_bounds(pw2, dy2, d, B * Kq, d, rm_dy2)
         dy_bf = dy2.dtype == torch.int16
         # bf16 mode (C5): dU is stored in bf16 by the FFN2 dgrad epilogue (OT_EPI_C_BF16); its two consumers,
         # the FFN1 dgrad (bf16 A, plane GEMM) and the W1 weight gradient (OT_WG_D_BF16), rounded it to bf16 at
@@ -480,14 +504,17 @@ class _Block(torch.autograd.Function):
         hbf = (torch.empty(B * Kq, f, dtype=torch.int16, device=dev)
                if h is None and fused2 and K.matmul_mode() == 'bf16' else None)
         if hbf is None:
-            with m.side(u if h is None else h, dy2):   # weight gradients overlap the dgrad chain on a second stream
+            with m.side(u if h is None else h, dy2, *keep):   # weight gradients overlap the dgrad chain (second stream)
                 K.wgrad(u if h is None else h, f, mt['rows'][1], dy2, d, mt['rows'][1], f, d, mt, nct, G,
                         m.g(f'blk.{l}.w2'), f * d, m.g(f'blk.{l}.b2'), d,
                         a_xform=(OT_AX_GELU if h is None else OT_AX_BF16) | (OT_WG_D_BF16 if dy_bf else 0),
-                        accumulate=acc, device=dev,
-                        m_rows=maps['tail'].nrows, rowmap=maps['tail'],
+                        accumulate=acc, device=dev, m_rows=maps['tail'].nrows, rowmap=maps['tail'],
                         a_bound=b_u if h is None else None, d_bound=b_dy2)
-        b_du = am(3) if not du_bf else None
+        # does the FFN2 dgrad report dU's bound and row maxima?  (its whole-tile vector epilogue does)
+        du_rep = fused2 or (((bounds is not None and not du_bf) or pw2 or pw1) and f % TILE == 0)
+        b_du = out('du') if du_rep and not du_bf else None
+        rm_du = torch.empty(B * Kq, f // TILE, device=dev) if pw1 and du_rep else None
+        rep_du = dict(amax_out=b_du, rowabs_out=rm_du, rowabs_n=f // TILE if rm_du is not None else 0)
         if fused2:
             # d > 128: the FFN2 dgrad also emits rowdot[row][f-tile] = sum dU (U - b1) for the norm2 backward
             rowdot = torch.empty(B * Kq, f // TILE, device=dev)
@@ -496,41 +523,30 @@ class _Block(torch.autograd.Function):
                        epi=OT_EPI_GELU_BWD | OT_EPI_ROWDOT | cbf | (OT_EPI_AUX_BF16 if u.dtype == torch.int16 else 0),
                        bias=m.p(f'blk.{l}.b1'), bias_gstride=f, rowdot=rowdot, rowdot_n=f // TILE,
                        m_rows=maps['tail'].nrows, device=dev, bimg=m.bimg(f'blk.{l}.w2', 'dgrad'),
-                       gelu_out=hbf, ldgelu=f, amax_out=b_du, rowabs_out=rm_du,
-                       rowabs_n=rm_du.shape[1] if rm_du is not None else 0, **pa2)
+                       gelu_out=hbf, ldgelu=f, **rep_du, **pa2)
             if hbf is not None:
                 with m.side(hbf, dy2):
                     K.wgrad(hbf, f, mt['rows'][1], dy2, d, mt['rows'][1], f, d, mt, nct, G, m.g(f'blk.{l}.w2'),
                             f * d, m.g(f'blk.{l}.b2'), d, a_xform=OT_AX_BF16, accumulate=acc, device=dev,
                             m_rows=maps['tail'].nrows, rowmap=maps['tail'])
-        elif (b_du is not None or pw2 or pw1) and f % TILE == 0:   # (bounds need the whole-tile vector epilogue)
-            K.gemm_rms(OT_GEMM_NT, dy2, d, d, mt['rows'][1], m.p(f'blk.{l}.w2'), f * d, d, f, mt['tile_group'], nt, du,
-                       f, mt['rows'][1], epi=OT_EPI_GELU_BWD, aux=u, ldaux=f, m_rows=maps['tail'].nrows, device=dev,
-                       bimg=m.bimg(f'blk.{l}.w2', 'dgrad'), amax_out=b_du, rowabs_out=rm_du,
-                       rowabs_n=rm_du.shape[1] if rm_du is not None else 0, **pa2)
         else:
-            b_du = None
             K.gemm_rms(OT_GEMM_NT, dy2, d, d, mt['rows'][1], m.p(f'blk.{l}.w2'), f * d, d, f, mt['tile_group'], nt, du,
                        f, mt['rows'][1], epi=OT_EPI_GELU_BWD, aux=u, ldaux=f, m_rows=maps['tail'].nrows, device=dev,
-                       bimg=m.bimg(f'blk.{l}.w2', 'dgrad'), **pa2)
-            if rm_du is not None:
-                K.rows_absmax(du, f, B * Kq, f, rm_du := torch.empty(B * Kq, (f + 255) // 256, device=dev))
-        pa1 = dict(a_rowmax=rm_du, a_rowmax_n=rm_du.shape[1]) if pw1 else {}
-        rm_dyo = torch.empty(B * Kq, (d + TILE - 1) // TILE, device=dev) if pwo else None
+                       bimg=m.bimg(f'blk.{l}.w2', 'dgrad'), **rep_du, **pa2)
+        pa1 = a_row_bounds(pw1, du, f, B * Kq, f, rm_du)
         a1n = x1n is not None and du_bf               # both operands bf16: the copy-staged weight gradient
-        with m.side(x1n if a1n else x1, du, rstd2):
+        with m.side(x1n if a1n else x1, du, rstd2, *keep):
             K.wgrad(x1n if a1n else x1, d, mt['rows'][1], du, f, mt['rows'][1], d, f, mt, nct, G, m.g(f'blk.{l}.w1'),
-                    d * f, m.g(f'blk.{l}.b1'), f,
-                    a_xform=(OT_AX_BF16 if a1n else OT_AX_RMSNORM) | (OT_WG_D_BF16 if du_bf else 0), rstd=rstd2,
-                    gamma=m.p(f'blk.{l}.norm2'),
+                    d * f, m.g(f'blk.{l}.b1'), f, rstd=rstd2, gamma=m.p(f'blk.{l}.norm2'),
+                    a_xform=(OT_AX_BF16 if a1n else OT_AX_RMSNORM) | (OT_WG_D_BF16 if du_bf else 0),
                     accumulate=acc, device=dev, m_rows=maps['tail'].nrows, rowmap=maps['tail'], d_bound=b_du)
         # FFN1 dgrad -> norm2 backward + residual; emit mask(dx1) for the attention branch
         dx1 = torch.empty(B * Kq, d, device=dev)
         dyo = torch.empty(B * Kq, d, device=dev) if rate > 0 else dx1
-        dyo_rows = False                       # did the FFN1 dgrad's epilogue write dyo's row maxima (rm_dyo)?
-        if m.fuse_bwd or rowdot is not None:   # FFN1 dgrad -> norm2 backward in the epilogue
-            b_dyo = am(4)
-            dyo_rows = rm_dyo is not None
+        dx1_ep = m.fuse_bwd or rowdot is not None   # FFN1 dgrad -> norm2 backward in the epilogue, which reports on dyo
+        rm_dyo = torch.empty(B * Kq, (d + TILE - 1) // TILE, device=dev) if pwo and dx1_ep else None
+        b_dyo = out('dyo') if dx1_ep else None
+        if dx1_ep:
             K.gemm_rms(OT_GEMM_NT, du, f, f, mt['rows'][1], m.p(f'blk.{l}.w1'), d * f, f, d, mt['tile_group'], nt,
                        dx1, d, mt['rows'][1], epi=OT_EPI_RMSNORM_BWD | (OT_EPI_DROPOUT if rate > 0 else 0),
                        a_xform=OT_AX_BF16 if du_bf else 0,
@@ -549,15 +565,13 @@ class _Block(torch.autograd.Function):
                           dx_masked=dyo if rate > 0 else None, lddxm=d, seed=seed, site=2 * l, drop=rate,
                           tail=tail, dgamma=m.g(f'blk.{l}.norm2'), accumulate=acc, device=dev)
         # Wo
-        with m.side(o, dyo):
+        with m.side(o, dyo, *keep):
             _wgrad_single(m, o, dyo, d, d, mt, m.g(f'blk.{l}.wo'), acc, dev, maps['tail'].nrows, maps['tail'],
                           a_bound=b_o, d_bound=b_dyo)
         do = torch.empty(B * Kq, d, device=dev)
-        if pwo and not dyo_rows:                     # dX1 came from the row-wise norm backward: its maxima here
-            K.rows_absmax(dyo, d, B * Kq, d, rm_dyo := torch.empty(B * Kq, (d + 255) // 256, device=dev))
         K.gemm_rms(OT_GEMM_NT, dyo, d, d, mt['rows'][1], m.p(f'blk.{l}.wo'), 0, d, d, mt['tile_group'], nt, do, d,
                    mt['rows'][1], epi=0, m_rows=maps['tail'].nrows, device=dev, bimg=m.bimg(f'blk.{l}.wo', 'dgrad'),
-                   **(dict(a_rowmax=rm_dyo, a_rowmax_n=rm_dyo.shape[1]) if pwo else {}))
+                   **a_row_bounds(pwo, dyo, d, B * Kq, d, rm_dyo))   # (a row-wise norm backward reports no maxima)
         # attention
         # bf16 mode, key-grouped backward (C5): dQKV in bf16 (OT_ATTN_DQKV_BF16) — the QKV dgrad (bf16 A) and
         # the Wqkv weight gradient (OT_WG_D_BF16) round it to bf16 anyway: the same values, half the bytes
@@ -569,18 +583,15 @@ class _Block(torch.autograd.Function):
         if Kq < I:
             dqkv[:, :d].zero_()
         bwd_b = not dq_bf and K.attn_amax_supported(I, Kq, hd, qp, backward=True)
-        b_dq = am(5) if (am(5) is not None and bwd_b) else None
+        b_dq = out('dqkv') if bwd_b else None
         # the QKV dgrad on the fp16 pair: dQKV's row maxima [row][q / k / v][head] from the attention backward (the
         # dQ part of rows without a query stays 0), else the row-absmax pass
         pqkv = m.dgrad_pair(f'blk.{l}.wqkv')
         rm_dq = torch.zeros(B * I, 3 * H, device=dev) if pqkv and bwd_b else None
-        K.attn_bwd(qkv, 3 * d, o, do, lse, B, H, I, Kq, hd, dqkv, qpos=qp, dq_part_bf16=True, amax=b_dq,
-                   rowmax=rm_dq)
-        if pqkv and rm_dq is None:
-            K.rows_absmax(dqkv, 3 * d, B * I, 3 * d, rm_dq := torch.empty(B * I, (3 * d + 255) // 256, device=dev))
-        pa_q = dict(a_rowmax=rm_dq, a_rowmax_n=rm_dq.shape[1]) if pqkv else {}
+        K.attn_bwd(qkv, 3 * d, o, do, lse, B, H, I, Kq, hd, dqkv, qpos=qp, dq_part_bf16=True, amax=b_dq, rowmax=rm_dq)
+        pa_q = a_row_bounds(pqkv, dqkv, 3 * d, B * I, 3 * d, rm_dq)
         an1 = xn1 is not None and dq_bf
-        with m.side(xn1 if an1 else x, dqkv, rstd1):
+        with m.side(xn1 if an1 else x, dqkv, rstd1, *keep):
             K.wgrad(xn1 if an1 else x, d, ma['rows'][0], dqkv, 3 * d, ma['rows'][0], d, 3 * d, ma, nca, G,
                     m.g(f'blk.{l}.wqkv'), 3 * d * d, None, 0,
                     a_xform=(OT_AX_BF16 if an1 else OT_AX_RMSNORM) | (OT_WG_D_BF16 if dq_bf else 0), rstd=rstd1,
@@ -606,7 +617,7 @@ class _Block(torch.autograd.Function):
         m.side_block_done()
         if m.grad_ready is not None:
             m.grad_ready(l)                     # this block's banks are final: the DP exchange may start
-        return None, dx, None, None, None, None, None, None, None, None
+        return None, dx, None, None, None, None, None, None, None, None, None
 
 
 def _wgrad_single(m, A, D, K_, N, mt, dW, acc, dev, mrows=0, rowmap=None, a_bound=None, d_bound=None):
@@ -812,8 +823,7 @@ class OneTransModel(nn.Module):
         self.f_ns = cfg.ns_input_width()
         # split mode: the FFN2 / FFN1 / Wo dgrad GEMMs on the scaled fp16 pair (pair-form dgrad images, the A rows'
         # maxima from their producers; ONETRANS_PAIR_DGRAD=0: the six-product split)
-        self.pair_dgrad = os.environ.get('ONETRANS_PAIR_DGRAD', '1') != '0'
-        self.layout = FlatLayout(cfg, self.f_ns, pair_dgrad=self.pair_dgrad)
+        self.layout = FlatLayout(cfg, self.f_ns, pair_dgrad=os.environ.get('ONETRANS_PAIR_DGRAD', '1') != '0')
         self.cfg_Lnsd = cfg.num_ns_tokens * cfg.hidden_dim
         self.flat = nn.Parameter(torch.zeros(self.layout.total, device=self.device))
         self.flat.grad = torch.zeros_like(self.flat)
@@ -851,11 +861,9 @@ class OneTransModel(nn.Module):
         # block weight gradients run on a second stream, overlapping the dgrad chain
         self.overlap_wgrad = True            # bench.py --no-overlap turns it off for standalone kernel traces
         # split mode: weight gradients on the scaled fp16 pair (ot_mixed_gemm_wgrad_ex) wherever the operands'
-        # producers report a magnitude bound: per layer [|O|, |U|, |dY2|, |dU|, |dX1 masked|, |dQKV|] (amax_slot),
-        # zeroed at every forward, folded in atomically by the producing kernels (ONETRANS_PAIR_WGRAD=0: the exact
-        # six-product split everywhere)
+        # producers report a magnitude bound (PairBounds, one per forward that a backward can follow;
+        # ONETRANS_PAIR_WGRAD=0: the exact six-product split everywhere)
         self.pair_wgrad = os.environ.get('ONETRANS_PAIR_WGRAD', '1') != '0'
-        self._amax = None
         self._side = None
         self._side_used = False
         self._side_keep: List[torch.Tensor] = []
@@ -929,31 +937,20 @@ class OneTransModel(nn.Module):
             return True
         return all(self.bimg(n, o) is not None for (n, o) in images)
 
+    @property
+    def pair_dgrad(self) -> bool:
+        """ONETRANS_PAIR_DGRAD as the layout's images were built with it (read-only: the images do not change)."""
+        return self.layout.pair_dgrad
+
     def gemm_pair(self, name: str, orient: str) -> bool:
-        """Is ``name``'s ``orient`` image one of the scaled-fp16-pair forms that need the A rows' maxima (a_rowmax: the
-        dgrad images and the Wo forward image under ONETRANS_PAIR_DGRAD, split mode)?"""
-        return (K.matmul_mode() == 'split' and self.pair_dgrad and (name, orient) in self.layout.pair_images
+        """Is ``name``'s ``orient`` image one of the scaled-fp16-pair forms that need the A rows' maxima (a_row_bounds:
+        the dgrad images and the Wo forward image under ONETRANS_PAIR_DGRAD, split mode)?"""
+        return (K.matmul_mode() == 'split' and (name, orient) in self.layout.pair_images
                 and self.bimg(name, orient) is not None and not (orient == 'fwd' and not name.endswith('.wo')))
 
     def dgrad_pair(self, name: str) -> bool:
-        """Is ``name``'s dgrad image in the scaled-fp16-pair form (split mode, ONETRANS_PAIR_DGRAD), so its dgrad GEMM
-        must get its A rows' maxima (a_rowmax)?"""
+        """Is ``name``'s dgrad image in the scaled-fp16-pair form, so its dgrad GEMM must get its A rows' maxima?"""
         return self.gemm_pair(name, 'dgrad')
-
-    def u_bound_ok(self, l: int) -> bool:
-        """Did block l's FFN1 forward report |U| (amax slot 1)?  It does on the pair-form W2 path (the plane GEMM with
-        row maxima, _block_forward's ``pair_w2``)."""
-        return (self.amax_slot(l, 1) is not None and self.bimg(f'blk.{l}.w2') is not None
-                and (f'blk.{l}.w2', 'fwd') in self.layout.pair_images)
-
-    def amax_slot(self, l: int, i: int) -> Optional[torch.Tensor]:
-        """One float of layer l's magnitude bounds (slots: 0 |O|, 1 |U|, 2 |dY2|, 3 |dU|, 4 |dX1 masked|, 5 |dQKV|),
-        or None outside the split mode / with ONETRANS_PAIR_WGRAD=0."""
-        if not self.pair_wgrad or K.matmul_mode() != 'split':
-            return None
-        if self._amax is None:
-            self._amax = torch.zeros(self.config.num_layers, 8, device=self.device)
-        return self._amax[l, i:i + 1]
 
     def x16_on(self, d: int) -> bool:
         """Store bf16 copies of the residual stream for the next GEMM's A (bf16 mode, plane GEMMs)?"""
@@ -1391,8 +1388,7 @@ class OneTransModel(nn.Module):
     def forward_probs(self, ns, seq, training: bool) -> torch.Tensor:
         """All tasks as one [T, B] tensor (the trainer's fused loss consumes it)."""
         plan = self._plan(ns, seq, training)
-        if self._amax is not None:
-            self._amax.zero_()                   # the producers of this step fold their output maxima in
+        bounds = PairBounds.begin(self.config.num_layers, self.device, K.matmul_mode(), self.pair_wgrad)
         seed = 0
         if training:
             self._step += 1
@@ -1406,7 +1402,7 @@ class OneTransModel(nn.Module):
             Kq = s['keep'] if l < nl - 1 else 1
             select = l < nl - 1 and Kq < s['in_len']         # a pyramid keep (the last layer: DCE, tail)
             x, rstd = _Block.apply(self.flat, x, self, l, s['in_len'], Kq, layer_seed(seed, b0, s['in_len'],
-                                   self.config.hidden_dim), training, rstd, select)
+                                   self.config.hidden_dim), training, rstd, select, bounds)
         probs, logits = _Head.apply(self.flat, x, self)
         probs._ot_logits = logits            # keras_bce_loss takes the BCE from the logits (Keras _keras_logits)
         return probs

@@ -246,8 +246,6 @@ def forward_probs_requests(m, ns: Dict, seq: Dict, req, training: bool = False, 
     plan_n = m._plan(ns, {}, training)
     if plan_s['seq_map'] is None:
         raise ValueError('forward_requests: no configured sequence feature in seq_features')
-    if m._amax is not None:
-        m._amax.zero_()
     seed = 0
     if training:
         m._step += 1

@@ -842,6 +842,36 @@ def test_dropout_apply_bf16(dev):
     assert 0.05 < (ref == 0).float().mean().item() < 0.15
 
 
+def test_dropout_rowmax_supported():
+    """ot_dropout_rowmax_supported: d / 4 a power of two or a multiple of 64 (the kernel's lane groups)."""
+    assert [K.dropout_rowmax_supported(d) for d in (128, 256, 512, 384, 192)] == [True, True, True, False, False]
+
+
+@pytest.mark.parametrize('d', [128, 256, 384, 512])
+def test_dropout_apply_magnitudes(dev, d):
+    """ot_dropout_apply_ex's amax / rowmax and ot_rows_absmax against the stored output (maxima are order-free:
+    exact), at a row count that fills no whole block; the output itself bit for bit ot_dropout_apply's.  Where the
+    dropout reports no row maxima (ot_dropout_rowmax_supported, d = 384) it still reports amax."""
+    rows, rate, parts = 37, 0.25, (d + 255) // 256
+    src = torch.randn(rows, d, generator=torch.Generator().manual_seed(d)).to(dev)
+    plain, dst = torch.empty(rows, d, device=dev), torch.empty(rows, d, device=dev)
+    amax = torch.zeros(1, device=dev)
+    ok = K.dropout_rowmax_supported(d)
+    rowmax = torch.full((rows, parts), -1.0, device=dev) if ok else None
+    absmax = torch.full((rows, parts), -1.0, device=dev)
+    K.dropout_apply(src, d, plain, d, rows, d, 1234, 7, rate, (1, 1))
+    K.dropout_apply(src, d, dst, d, rows, d, 1234, 7, rate, (1, 1), amax=amax, rowmax=rowmax)
+    K.rows_absmax(dst, d, rows, d, absmax)
+    torch.cuda.synchronize()
+    assert torch.equal(dst, plain)
+    assert 0.15 < (dst == 0).float().mean().item() < 0.35
+    ref = torch.stack([dst[:, 256 * p:256 * p + 256].abs().amax(dim=1) for p in range(parts)], dim=1)
+    assert torch.equal(absmax, ref)
+    assert amax.item() == dst.abs().max().item()
+    if ok:
+        assert torch.equal(rowmax, ref)
+
+
 @pytest.mark.parametrize('K_', [1, 3])
 def test_attn_bwd_small_bf16_dqkv(dev, K_):
     """Short-tail attention backward (K <= 4, the last layer after DCE) with bf16 dqkv

@@ -59,11 +59,20 @@ CASES = {
     # d = 512 (C5's width, hd 64): the fused norm epilogues span 4 column tiles (per-tile partials)
     'criteo_d512_pyramid': lambda: small_criteo('tail', pyramid=True, layers=2, d=512, H=8, f=1024, Lns=4,
                                                 seq_lens=(12, 9, 7)),
+    # d = 384 (hd 64): d / 4 = 96 lanes per row, neither a power of two nor a multiple of 64 — the dropout reports no
+    # row maxima (ot_dropout_rowmax_supported) and the FFN2 dgrad takes them from the row-absmax pass
+    'criteo_d384_pyramid': lambda: with_dropout(small_criteo('tail', pyramid=True, layers=2, d=384, H=6, f=768, Lns=4,
+                                                             seq_lens=(12, 9, 7))),
 }
 
 
 def norm_select(cfg):
     cfg.pyramid_select = 'norm'
+    return cfg
+
+
+def with_dropout(cfg):
+    cfg.dropout_rate = cfg.dropout_rate or 0.1
     return cfg
 
 
@@ -100,7 +109,7 @@ def ns_t(d, dev):
 
 @pytest.mark.parametrize('case', ['c1_head', 'criteo_head', 'criteo_tail_pyramid', 'criteo_d128_hd32',
                                   'criteo_d128_pyramid', 'criteo_norm_pyramid', 'criteo_d128_norm_pyramid',
-                                  'criteo_d256_pyramid', 'criteo_d512_pyramid'])
+                                  'criteo_d256_pyramid', 'criteo_d512_pyramid', 'criteo_d384_pyramid'])
 @pytest.mark.parametrize('training', [False, True])
 def test_gradient_parity(dev, case, training):
     cfg = CASES[case]()
@@ -173,6 +182,74 @@ def check_grads(cfg, B, dev, training):
         dense.index_add_(0, keys.cpu(), grads.double().cpu())
         scale = max(1e-3, rg[tname].abs().max().item())
         assert (dense - rg[tname]).abs().max().item() / scale < 2e-4, tname
+
+
+def _interleave_setup(dev):
+    """criteo_d128_pyramid with dropout 0.1, two batches and a factory of equal fresh models.  The second batch has
+    another size than the first: a forward stages its inputs in the buffers of its input shapes' plan, and the model
+    refuses a backward whose plan a later forward of the same shapes has overwritten (_Tokenize)."""
+    cfg = with_dropout(CASES['criteo_d128_pyramid']())
+    assert cfg.dropout_rate == 0.1
+    P = init_params(cfg, cfg.ns_input_width(), seed=0, perturb=True)
+    batches = [make_batch(37, cfg, seed=1000), make_batch(41, cfg, seed=2000)]
+
+    def fresh(step=0):
+        model = OneTransModel(cfg, device=dev, init=P)
+        model._step = step
+        return model
+
+    def forward(model, batch, training=True):
+        ns, seq, lab = batch
+        probs = model.forward_probs(ns_t(ns, dev), ns_t(seq, dev), training=training)
+        return keras_bce_loss(stack_labels(lab, cfg.tasks, dev), probs, cfg.tasks)
+
+    def grads(model):
+        torch.cuda.synchronize()
+        return ({n: model.g(n).clone() for n in model.layout.shapes},
+                [(t, k.clone(), g.clone()) for (t, k, g) in model._pending_sparse])
+
+    return batches, fresh, forward, grads
+
+
+def _assert_same_grads(a, b):
+    assert a[0].keys() == b[0].keys() and len(a[1]) == len(b[1]) > 0
+    for n in a[0]:
+        assert torch.equal(a[0][n], b[0][n]), n
+    for (ta, ka, ga), (tb, kb, gb) in zip(a[1], b[1]):
+        assert ta == tb and torch.equal(ka, kb) and torch.equal(ga, gb), ta
+
+
+def test_evaluation_forward_between_forward_and_backward(dev):
+    """A training step's gradients are bit for bit the same with an evaluation forward of another batch between
+    its forward and its backward: the fp16-pair bounds belong to one forward and its backward (PairBounds)."""
+    (b1, b2), fresh, forward, grads = _interleave_setup(dev)
+    m = fresh()
+    forward(m, b1).backward()
+    alone = grads(m)
+    m = fresh()
+    loss = forward(m, b1)
+    with torch.no_grad():
+        forward(m, b2, training=False)
+    loss.backward()
+    _assert_same_grads(alone, grads(m))
+
+
+def test_two_forwards_then_both_backwards(dev):
+    """Two training forwards, then both backwards in reverse order (gradients written, not accumulated, and copied
+    out in between): each step's gradients bit for bit those of the step run alone."""
+    (b1, b2), fresh, forward, grads = _interleave_setup(dev)
+    alone = []
+    for step, b in enumerate((b1, b2)):
+        m = fresh(step)                    # the second step draws the dropout masks of step 2
+        forward(m, b).backward()
+        alone.append(grads(m))
+    m = fresh()
+    assert not m.accumulate_grads
+    l1, l2 = forward(m, b1), forward(m, b2)
+    l2.backward()
+    _assert_same_grads(alone[1], grads(m))
+    l1.backward()
+    _assert_same_grads(alone[0], grads(m))
 
 
 def test_regression_task_mse(dev):
