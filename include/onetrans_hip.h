@@ -447,6 +447,40 @@ int ot_attn_bwd_cached(const float* qkv, int64_t ld, const float* kv_cache, int6
                        const float* lse, float* dqkv, float* dkv_cache, int accumulate, void* workspace,
                        size_t ws_bytes, void* stream);
 
+/* ---- padding mask (attention.hip, seqfuse.hip) ---------------------------------------------
+ * Variable-length histories: behaviour sequences arrive left-padded to their cap, and with a key-padding mask a
+ * padding event is no key for any other token.  key_valid is a byte per (sample, key): key_valid[b * ldv + j] != 0
+ * when key j of sample b is a real token (ldv >= I; a layer of I tokens under the tail keep reads layer 0's array
+ * through a pointer offset L0 - I with ldv = L0).  Query at position i sees key j iff j <= i and (valid j or
+ * j == i): the self exception gives every row one visible key (no empty softmax), and since a valid row never sees
+ * an invalid key, a padding row's content reaches no valid row in any layer.  A padding query's output is its own v.
+ *
+ * ot_attn_fwd_masked / ot_attn_bwd_masked: ot_attn_fwd / ot_attn_bwd with that rule (same operands, outputs, lse
+ * convention and ot_attn_bwd_workspace_size workspace).  They run the generic f32 family at every shape for
+ * OT_MATMUL_F32 and OT_MATMUL_SPLIT_BF16 (short-tail kernels at K <= 4, else the f32 MFMA forward and the prep +
+ * f32 MFMA backward; results do not depend on which of the two precisions is named); OT_MATMUL_BF16 returns
+ * OT_ERR_UNSUPPORTED.  No magnitude bounds are reported.
+ * ot_attn_fwd_cached_masked: ot_attn_fwd_cached / ot_attn_fwd_cached_lse (lse_or_null) with cache_valid
+ * [R][ldcv >= Ic] bytes over the cached rows; a candidate's own n rows are always valid.
+ *
+ * ot_seq_key_valid writes layer 0's array valid0 [B][L0] in one stream-ordered launch (no host sync).  lens: device
+ * int32 [nseq][B], the number of real events of each present sequence (the last lens of its seq_len[i] positions;
+ * values outside [0, seq_len[i]] are clamped on the device).  seq_len / seq_off: HOST arrays [nseq], each sequence's
+ * cap and the token position of its first event (ascending, disjoint).  Every token outside the segments ([SEP], NS)
+ * is valid.  rank NULL: event j of sequence i sits at seq_off[i] + j.  rank given (time fusion: ot_seq_time_rows'
+ * rank_out, row stride ldr): it sits at rank[b * ldr + start_i + j], start_i = seq_len[0] + .. + seq_len[i-1]; the
+ * segments must then be the positions 0 .. sum(seq_len) - 1 without gaps.  nseq <= 32. */
+int ot_attn_fwd_masked(const float* qkv, int64_t ld, int B, int H, int I, int K, const int32_t* qpos, int head_dim,
+                       const uint8_t* key_valid, int64_t ldv, float* out, float* lse, int precision, void* stream);
+int ot_attn_bwd_masked(const float* qkv, int64_t ld, const float* out, const float* dout, const float* lse, int B,
+                       int H, int I, int K, const int32_t* qpos, int head_dim, const uint8_t* key_valid, int64_t ldv,
+                       float* dqkv, float* delta_ws, int precision, void* stream);
+int ot_attn_fwd_cached_masked(const float* qkv, int64_t ld, const float* kv_cache, int64_t ldc, const int32_t* req,
+                              int C, int H, int Ic, int n, int Kq, int head_dim, const uint8_t* cache_valid,
+                              int64_t ldcv, float* out, float* lse_or_null, void* stream);
+int ot_seq_key_valid(const int32_t* lens, const int32_t* seq_len, const int32_t* seq_off, int nseq, int B, int L0,
+                     const int32_t* rank, int64_t ldr, uint8_t* valid0, void* stream);
+
 /* ---- pyramid query selection (pyramid.hip) -----------------------------------------------
  * Replaces PyramidScheduler.get_layer_config + tf.gather (model.py:287-302, 356, 371): per sample,
  * keep the K of I tokens with the largest key (score[b*I+p] * score_sign, ties to the later

@@ -202,6 +202,11 @@ SIGNATURES = {
     'ot_rank_topk': (c_int, [P, I64, c_int, P, c_int, P, I64, c_int, c_int, P, P, P, P, P, c_size_t, P]),
     'ot_seq_time_rows_workspace_size': (c_size_t, [c_int, c_int, c_int]),
     'ot_seq_time_rows': (c_int, [P, c_int, c_int, c_int, I64, P, P, P, P, c_size_t, P]),
+    'ot_attn_fwd_masked': (c_int, [P, I64, c_int, c_int, c_int, c_int, P, c_int, P, I64, P, P, c_int, P]),
+    'ot_attn_bwd_masked': (c_int, [P, I64, P, P, P, c_int, c_int, c_int, c_int, P, c_int, P, I64, P, P, c_int, P]),
+    'ot_attn_fwd_cached_masked': (c_int, [P, I64, P, I64, P, c_int, c_int, c_int, c_int, c_int, c_int, P, I64, P, P,
+                                          P]),
+    'ot_seq_key_valid': (c_int, [P, P, P, c_int, c_int, c_int, P, I64, P, P]),
     'ot_ns_bag_pool': (c_int, [P, c_int, c_int, P, I64, P, P]),
     'ot_ns_bag_grad_pack': (c_int, [P, c_int, c_int, P, I64, P, P, P, P]),
 }

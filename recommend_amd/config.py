@@ -118,6 +118,12 @@ class OneTransConfig:
         # needs integer times ``seq_features[name + seq_time_suffix]`` [B, L_name] (DESIGN.md §Sequence fusion)
         self.seq_fusion = 'sep'
         self.seq_time_suffix = '_time'
+        # build: variable-length histories.  On: each present sequence ``name`` carries
+        # ``seq_features[name + seq_len_suffix]``, an integer [B] count of real events (the last ``len`` positions, as
+        # SequenceProcessor.pad_batch lays them out), and padding events are masked out as attention keys.  Off (the
+        # reference): a padding event is an ordinary token and nothing new is read
+        self.seq_padding_mask = False
+        self.seq_len_suffix = '_len'
 
     # ------------------------------------------------------------------ helpers
     def to_dict(self) -> Dict:
@@ -315,6 +321,21 @@ def check_seq_fusion(cfg: OneTransConfig) -> None:
         raise ValueError(f"unknown seq_fusion {mode!r}: expected 'sep' or 'time'")
     if mode == 'time' and not getattr(cfg, 'seq_time_suffix', '_time'):
         raise ValueError("seq_fusion='time' needs a non-empty seq_time_suffix")
+
+
+def check_padding_mask(cfg: OneTransConfig) -> None:
+    """``seq_padding_mask`` runs the masked f32-accurate attention kernels over tail keeps only: the reduced-precision
+    attention kernels carry no mask, and a score-based pyramid keep would have to exclude padding tokens."""
+    if not getattr(cfg, 'seq_padding_mask', False):
+        return
+    if not getattr(cfg, 'seq_len_suffix', '_len'):
+        raise ValueError('seq_padding_mask needs a non-empty seq_len_suffix')
+    if getattr(cfg, 'compute_dtype', 'fp32') in ('bf16', 'fp8attn'):
+        raise NotImplementedError(f"seq_padding_mask with compute_dtype {cfg.compute_dtype!r}: the bf16 and fp8 "
+                                  "attention kernels carry no padding mask; use compute_dtype 'fp32'")
+    if getattr(cfg, 'pyramid_select', 'tail') == 'norm':
+        raise ValueError("seq_padding_mask with pyramid_select='norm': a score-based keep would have to exclude "
+                         "padding tokens (not implemented); use pyramid_select='tail'")
 
 
 BAG_POOLINGS = ('sum', 'mean')

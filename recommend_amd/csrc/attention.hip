@@ -62,6 +62,9 @@ struct AttnArgs {
   // short-tail backward, f32 dqkv (fp16-pair consumers' bounds): max |dQKV| folded in (one float, zeroed by the
   // caller) and the per-row maxima [B*I][3][H] (dQ / dK / dV part per head; the caller zeroes the array)
   float* amax; float* rowmax;
+  // key-padding mask (the MASK instantiations only: ot_attn_fwd_masked / ot_attn_bwd_masked): key_valid[b * ldv + j]
+  // != 0 when key j of sample b is a real token; query i sees key j iff j <= i and (valid j or j == i)
+  const uint8_t* key_valid; int64_t ldv;
 };
 
 // position of kept query j (< K) of the sample whose qpos slice is qp (null: the tail rule)
@@ -164,7 +167,13 @@ __device__ __forceinline__ void load_frag_clamped(float (&f)[HD / 2], const floa
 // q element) so the online softmax uses v_exp_f32 directly; the causal mask is applied on the
 // diagonal key block only (earlier blocks are fully visible); K/V rows past the end are loaded from
 // a clamped row (finite) and removed by the mask, so the loads carry no branches.
-template <int HD>
+// MASK: the key-padding mask (AttnArgs.key_valid).  The lanes ballot the key block's 32 validity bytes once and every
+// accumulator row tests its key's bit; the causal select then runs on every key block (an earlier block is no longer
+// fully visible).  A query may see nothing in a block, or in every block before its own position (a padding prefix),
+// so the running maximum can still be -inf after a block: the exponents are then taken against 0 instead (every term
+// exp2(-inf) = 0, corr = 0 on an accumulator that is still 0), which keeps -inf - (-inf) out of the online softmax.
+// The query's own key is always visible, so m and l are finite and positive by the end of the row.
+template <int HD, bool MASK = false>
 __global__ __launch_bounds__(256) void attn_fwd_kernel(AttnArgs p) {
   __shared__ __attribute__((aligned(16))) float lds[4][32 * TLD<HD>()];
   const int lane = threadIdx.x & 63, li = lane & 31, hh = lane >> 5;
@@ -177,6 +186,8 @@ __global__ __launch_bounds__(256) void attn_fwd_kernel(AttnArgs p) {
   const float* Kp = Q + p.d;
   const float* V = Q + 2 * p.d;
   const int32_t* qp = p.qpos ? p.qpos + (int64_t)b * K : nullptr;
+  const uint8_t* kvp = nullptr;
+  if constexpr (MASK) kvp = p.key_valid + (int64_t)b * p.ldv;
   const int nqb = (K + 31) / 32;
   const float qscale = p.scale * 1.4426950408889634f;   // log2(e) / sqrt(hd)
   for (int qb = 0; qb < nqb; ++qb) {
@@ -207,7 +218,15 @@ __global__ __launch_bounds__(256) void attn_fwd_kernel(AttnArgs p) {
 #endif
       frag_to_lds<HD>(tV, vf, li, hh);
       f32x16 s = mm_frag<HD>(kf, qf);               // S^T (log2 units): row = key, col = query
-      if (OT_ATTN_FWD_MASKALL || kb >= first_masked) {
+      if constexpr (MASK) {
+        const int kk = key0 + li;                     // lanes li and li + 32 read the same byte: bits 0..31 are the block
+        const uint32_t vm = (uint32_t)__ballot(kk < I && kvp[kk] != 0);
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+          const int kr = acc_row(r, hh), key = key0 + kr;
+          s[r] = (key <= qpos && (((vm >> kr) & 1u) || key == qpos)) ? s[r] : -INFINITY;
+        }
+      } else if (OT_ATTN_FWD_MASKALL || kb >= first_masked) {
 #pragma unroll
         for (int r = 0; r < 16; ++r)
           s[r] = (key0 + acc_row(r, hh) <= qpos) ? s[r] : -INFINITY;   // kpos <= qpos < I
@@ -216,12 +235,15 @@ __global__ __launch_bounds__(256) void attn_fwd_kernel(AttnArgs p) {
 #pragma unroll
       for (int r = 1; r < 16; ++r) mloc = fmaxf(mloc, s[r]);
       mloc = fmaxf(mloc, __shfl_xor(mloc, 32, 64));
-      const float mnew = fmaxf(m, mloc);            // finite: key 0 is always visible
-      const float corr = __builtin_amdgcn_exp2f(m - mnew);
+      // un-masked: finite from the first block on (key 0 is visible to every query).  MASK: -inf until the row's first
+      // visible key; the exponents below are then taken against 0 (see the kernel's header)
+      const float mnew = fmaxf(m, mloc);
+      const float msub = MASK && mnew == -INFINITY ? 0.f : mnew;
+      const float corr = __builtin_amdgcn_exp2f(m - msub);
       float lsum = 0.f;
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
-        const float e = __builtin_amdgcn_exp2f(s[r] - mnew);
+        const float e = __builtin_amdgcn_exp2f(s[r] - msub);
         s[r] = e;
         lsum += e;
       }
@@ -620,10 +642,14 @@ constexpr int BWD_WAVES() { return HD >= 128 ? 2 : 4; }
 // block's lse (+inf past K); both go to a per-wave LDS row that the later key blocks read.  The prep
 // launch and its re-read of dO disappear (C2: 87 us per layer).
 constexpr int FDL_KP = 160;
-template <int HD, bool SEL, int DS = 1, bool FDL = false>
+// MASK: the key-padding mask (AttnArgs.key_valid).  The key is on the lane: one byte load per key block, and the
+// forward's predicate (key <= query and (valid key or key == query)) selects P before it is used (before exp's
+// value can matter: an invisible key's exponent may overflow, and the select drops it).
+template <int HD, bool SEL, int DS = 1, bool FDL = false, bool MASK = false>
 __global__ __launch_bounds__(DS == 1 ? 64 * BWD_WAVES<HD>() : 64 * DS, 2)   // 2 waves per SIMD
 void attn_bwd_kernel(AttnArgs p) {
   static_assert(!FDL || (DS == 1 && !SEL), "attn_bwd_kernel: in-kernel row statistics need DS = 1, tail queries");
+  static_assert(!FDL || !MASK, "attn_bwd_kernel: the masked backward takes its row statistics from the prep kernel");
   constexpr int LD = TLD<HD>();
   constexpr int SLD = 36;                  // dS tile row stride (32 keys + pad)
   constexpr int PER_WAVE = 3 * 32 * LD + 32 * SLD;
@@ -686,6 +712,10 @@ void attn_bwd_kernel(AttnArgs p) {
     float kf[HD / 2], vf[HD / 2];
     BWD_LOAD<HD>(kf, Kp, p.ld, kpos, I, hh);
     BWD_LOAD<HD>(vf, V, p.ld, kpos, I, hh);
+    // MASK: this lane's key is seen by the queries at kpos .. khi — every later one when it is a real token, only
+    // itself when it is padding (one more compare per score, one register per lane)
+    int khi = 0x7fffffff;
+    if constexpr (MASK) khi = (kpos < I && p.key_valid[(int64_t)b * p.ldv + kpos] != 0) ? 0x7fffffff : kpos;
     frag_to_lds<HD>(tK, kf, li, hh);
     f32x16 dk[NB(HD)], dv[NB(HD)];
 #pragma unroll
@@ -775,7 +805,7 @@ void attn_bwd_kernel(AttnArgs p) {
           const int r = 4 * g + e, j = q0 + 8 * g + 4 * hh + e;
           const float ex = __expf(s[r] * p.scale - l4[g][e]);
           const int qposj = SEL ? qv[e] : q_off + j;
-          const float P = kpos <= qposj ? ex : 0.f;
+          const float P = (kpos <= qposj && (!MASK || qposj <= khi)) ? ex : 0.f;
           s[r] = P;
           dp[r] = P * (dp[r] - d4[g][e]) * p.scale;    // dS, pre-scaled by 1/sqrt(hd)
           tS[(8 * g + 4 * hh + e) * SLD + li] = dp[r];
@@ -1483,7 +1513,8 @@ constexpr int SMALL_K = 4;
 
 // KQ: the largest K the instance takes (1: the last layer's one query — a quarter of the registers, so more waves
 // per SIMD keep more K / V rows in flight)
-template <int HD, int KQ = SMALL_K>
+// MASK: the key-padding mask (AttnArgs.key_valid), one byte per key slot and pass.
+template <int HD, int KQ = SMALL_K, bool MASK = false>
 __global__ __launch_bounds__(256) void attn_bwd_small_kernel(AttnArgs p) {
   constexpr int LPK = HD / 4, KPW = 64 / LPK;
   const int lane = threadIdx.x & 63, sub = lane % LPK, slot = lane / LPK;
@@ -1528,6 +1559,8 @@ __global__ __launch_bounds__(256) void attn_bwd_small_kernel(AttnArgs p) {
       vvn = *reinterpret_cast<const f32x4*>(V + rn);
     }
     f32x4 dk = {0.f, 0.f, 0.f, 0.f}, dv = {0.f, 0.f, 0.f, 0.f};
+    bool kval = true;
+    if constexpr (MASK) kval = live && p.key_valid[(int64_t)b * p.ldv + key] != 0;
 #pragma unroll
     for (int j = 0; j < KQ; ++j) {
       if (j >= K) break;
@@ -1538,7 +1571,8 @@ __global__ __launch_bounds__(256) void attn_bwd_small_kernel(AttnArgs p) {
         sdot += __shfl_xor(sdot, off, 64);
         pdot += __shfl_xor(pdot, off, 64);
       }
-      const bool vis = live && key <= qpos[j];
+      bool vis = live && key <= qpos[j];
+      if constexpr (MASK) vis = vis && (kval || key == qpos[j]);
       const float P = vis ? __expf(sdot * p.scale - lse[j]) : 0.f;
       const float ds = vis ? P * (pdot - delta[j]) * p.scale : 0.f;
       dv += P * o[j];
@@ -1604,7 +1638,9 @@ __global__ __launch_bounds__(256) void attn_bwd_small_kernel(AttnArgs p) {
 // per pass, each slot with its own online softmax (running max m, sum l, output o; scores in log2 units) over the
 // keys it sees; the slots' states are merged at the end with xor shuffles (max, then rescaled sums).  Exact f32
 // products — no split.
-template <int HD, int KQ = SMALL_K>
+// MASK: the key-padding mask (AttnArgs.key_valid), one byte per key slot and pass; a slot that saw no key keeps
+// m = -inf and merges with weight 0, as a slot past the last key does without the mask.
+template <int HD, int KQ = SMALL_K, bool MASK = false>
 __global__ __launch_bounds__(256) void attn_fwd_small_kernel(AttnArgs p) {
   constexpr int LPK = HD / 4, KPW = 64 / LPK;
   const int lane = threadIdx.x & 63, sub = lane % LPK, slot = lane / LPK;
@@ -1645,13 +1681,15 @@ __global__ __launch_bounds__(256) void attn_fwd_small_kernel(AttnArgs p) {
       kvn = *reinterpret_cast<const f32x4*>(Kp + rn);
       vvn = *reinterpret_cast<const f32x4*>(V + rn);
     }
+    bool kval = true;
+    if constexpr (MASK) kval = live && p.key_valid[(int64_t)b * p.ldv + key] != 0;
 #pragma unroll
     for (int j = 0; j < KQ; ++j) {
       if (j >= K) break;
       float s = q[j].x * kv.x + q[j].y * kv.y + q[j].z * kv.z + q[j].w * kv.w;
 #pragma unroll
       for (int off = 1; off < LPK; off <<= 1) s += __shfl_xor(s, off, 64);
-      if (live && key <= qpos[j]) {                   // (uniform over the key's lanes)
+      if (live && key <= qpos[j] && (!MASK || kval || key == qpos[j])) {   // (uniform over the key's lanes)
         const float mn = fmaxf(m[j], s);
         const float corr = __builtin_amdgcn_exp2f(m[j] - mn), e = __builtin_amdgcn_exp2f(s - mn);
         l[j] = l[j] * corr + e;
@@ -1700,6 +1738,9 @@ struct AttnCachedArgs {
   int C, H, Ic, n, Kq, d;
   float scale;
   float* lse;                              // [C, H, Kq] natural-log row statistics for the backward, or null
+  // key-padding mask of the cached rows (the MASK instantiations only): cache_valid[r * ldcv + key], key < Ic; a
+  // candidate's own n rows are always valid
+  const uint8_t* cache_valid; int64_t ldcv;
 };
 
 template <int HD>
@@ -1717,7 +1758,9 @@ __device__ __forceinline__ void load_row_frag(float (&f)[HD / 2], const float* r
   }
 }
 
-template <int HD>
+// MASK: as attn_fwd_kernel's (ballot of the block's validity bits, select on every key block, the -inf guard); the
+// queries are N rows, whose own keys are valid, so the predicate needs no self exception.
+template <int HD, bool MASK = false>
 __global__ __launch_bounds__(256) void attn_fwd_cached_kernel(AttnCachedArgs p) {
   __shared__ __attribute__((aligned(16))) float lds[4][32 * TLD<HD>()];
   const int lane = threadIdx.x & 63, li = lane & 31, hh = lane >> 5;
@@ -1765,7 +1808,14 @@ __global__ __launch_bounds__(256) void attn_fwd_cached_kernel(AttnCachedArgs p) 
       load_row_frag<HD>(vf, vr, hh);
       frag_to_lds<HD>(tV, vf, li, hh);
       f32x16 s = mm_frag<HD>(kf, qf);               // S^T (log2 units): row = key, col = query
-      if (kb >= first_masked) {
+      if constexpr (MASK) {
+        const uint32_t vm = (uint32_t)__ballot(key < Ic ? p.cache_valid[r * p.ldcv + key] != 0 : key < L);
+#pragma unroll
+        for (int rr = 0; rr < 16; ++rr) {
+          const int kr = acc_row(rr, hh);
+          s[rr] = (32 * kb + kr <= qpos && ((vm >> kr) & 1u)) ? s[rr] : -INFINITY;
+        }
+      } else if (kb >= first_masked) {
 #pragma unroll
         for (int rr = 0; rr < 16; ++rr) s[rr] = (32 * kb + acc_row(rr, hh) <= qpos) ? s[rr] : -INFINITY;
       }
@@ -1774,11 +1824,12 @@ __global__ __launch_bounds__(256) void attn_fwd_cached_kernel(AttnCachedArgs p) 
       for (int rr = 1; rr < 16; ++rr) mloc = fmaxf(mloc, s[rr]);
       mloc = fmaxf(mloc, __shfl_xor(mloc, 32, 64));
       const float mnew = fmaxf(m, mloc);
-      const float corr = __builtin_amdgcn_exp2f(m - mnew);
+      const float msub = MASK && mnew == -INFINITY ? 0.f : mnew;   // MASK: no visible key yet (attn_fwd_kernel)
+      const float corr = __builtin_amdgcn_exp2f(m - msub);
       float lsum = 0.f;
 #pragma unroll
       for (int rr = 0; rr < 16; ++rr) {
-        const float e = __builtin_amdgcn_exp2f(s[rr] - mnew);
+        const float e = __builtin_amdgcn_exp2f(s[rr] - msub);
         s[rr] = e;
         lsum += e;
       }
@@ -2453,5 +2504,129 @@ static int attn_bwd_impl(const float* qkv, int64_t ld, const float* out, const f
     hipLaunchKernelGGL(kern, dim3(grid), dim3(64 * waves), 0, (hipStream_t)stream, p);
   }
   OT_LAUNCH_CHECK("ot_attn_bwd");
+  return OT_OK;
+}
+
+// ------------------------------------------------------------------------------------------
+// Key-padding mask (include/onetrans_hip.h, "padding mask").  A masked call runs the generic f32 family at every
+// shape, for both f32-accurate precisions: the short-tail kernels at K <= SMALL_K, else attn_fwd_kernel and
+// attn_bwd_prep_kernel + attn_bwd_kernel (head_dim 64 as two 32-dim waves), all in their MASK instantiations.  The
+// slice, split, bf16 and fp8 kernels carry no mask: OT_MATMUL_BF16 is refused.  No amax / rowmax is reported.
+static int attn_masked_check(const char* who, const void* key_valid, int64_t ldv, int B, int H, int I, int K,
+                             int64_t ld, int head_dim, int precision) {
+  if (precision == OT_MATMUL_BF16)
+    return fail(OT_ERR_UNSUPPORTED, "%s: the padding mask runs the f32-accurate kernels only (OT_MATMUL_F32 / "
+                "OT_MATMUL_SPLIT_BF16)", who);
+  OT_REQUIRE(precision == OT_MATMUL_F32 || precision == OT_MATMUL_SPLIT_BF16, "%s: unknown precision %d", who, precision);
+  OT_REQUIRE(B >= 0 && H > 0 && I > 0 && K > 0 && K <= I, "%s: bad sizes B=%d H=%d I=%d K=%d", who, B, H, I, K);
+  OT_REQUIRE(head_dim == 16 || head_dim == 32 || head_dim == 64 || head_dim == 128, "%s: head_dim %d unsupported", who,
+             head_dim);
+  OT_REQUIRE(ld % 4 == 0 && ld >= 3 * (int64_t)H * head_dim, "%s: ld must be >= 3d and a multiple of 4", who);
+  OT_REQUIRE(key_valid && ldv >= I, "%s: key_valid is null or ldv < I", who);
+  OT_REQUIRE((int64_t)B * H < (int64_t)1 << 31, "%s: grid too large", who);
+  return OT_OK;
+}
+
+#define OT_ATTN_MASKED_SMALL(KERNEL, HD_, K_, ...)                                           \
+  switch (HD_) {                                                                             \
+    case 16: if (K_ == 1) hipLaunchKernelGGL((KERNEL<16, 1, true>), __VA_ARGS__);            \
+             else hipLaunchKernelGGL((KERNEL<16, SMALL_K, true>), __VA_ARGS__); break;       \
+    case 32: if (K_ == 1) hipLaunchKernelGGL((KERNEL<32, 1, true>), __VA_ARGS__);            \
+             else hipLaunchKernelGGL((KERNEL<32, SMALL_K, true>), __VA_ARGS__); break;       \
+    case 64: if (K_ == 1) hipLaunchKernelGGL((KERNEL<64, 1, true>), __VA_ARGS__);            \
+             else hipLaunchKernelGGL((KERNEL<64, SMALL_K, true>), __VA_ARGS__); break;       \
+    default: if (K_ == 1) hipLaunchKernelGGL((KERNEL<128, 1, true>), __VA_ARGS__);           \
+             else hipLaunchKernelGGL((KERNEL<128, SMALL_K, true>), __VA_ARGS__); break;      \
+  }
+
+extern "C" int ot_attn_fwd_masked(const float* qkv, int64_t ld, int B, int H, int I, int K, const int32_t* qpos,
+                                  int head_dim, const uint8_t* key_valid, int64_t ldv, float* out, float* lse,
+                                  int precision, void* stream) {
+  if (int rc = attn_masked_check("ot_attn_fwd_masked", key_valid, ldv, B, H, I, K, ld, head_dim, precision)) return rc;
+  OT_REQUIRE(qkv && out && lse, "ot_attn_fwd_masked: null operand");
+  if (B == 0) return OT_OK;
+  AttnArgs p{qkv, ld, H * head_dim, nullptr, nullptr, out, lse, nullptr, nullptr, B, H, I, K,
+             1.f / sqrtf((float)head_dim), qpos};
+  p.key_valid = key_valid;
+  p.ldv = ldv;
+  const dim3 grid(ceil_div((int64_t)B * H, 4));
+  hipStream_t st = (hipStream_t)stream;
+  if (K <= SMALL_K && head_dim != 16) {                // the un-masked routing's short-tail forward shapes
+    OT_ATTN_MASKED_SMALL(attn_fwd_small_kernel, head_dim, K, grid, dim3(256), 0, st, p);
+  } else {
+    switch (head_dim) {
+      case 16: hipLaunchKernelGGL((attn_fwd_kernel<16, true>), grid, dim3(256), 0, st, p); break;
+      case 32: hipLaunchKernelGGL((attn_fwd_kernel<32, true>), grid, dim3(256), 0, st, p); break;
+      case 64: hipLaunchKernelGGL((attn_fwd_kernel<64, true>), grid, dim3(256), 0, st, p); break;
+      default: hipLaunchKernelGGL((attn_fwd_kernel<128, true>), grid, dim3(256), 0, st, p); break;
+    }
+  }
+  OT_LAUNCH_CHECK("ot_attn_fwd_masked");
+  return OT_OK;
+}
+
+extern "C" int ot_attn_bwd_masked(const float* qkv, int64_t ld, const float* out, const float* dout, const float* lse,
+                                  int B, int H, int I, int K, const int32_t* qpos, int head_dim,
+                                  const uint8_t* key_valid, int64_t ldv, float* dqkv, float* delta_ws, int precision,
+                                  void* stream) {
+  if (int rc = attn_masked_check("ot_attn_bwd_masked", key_valid, ldv, B, H, I, K, ld, head_dim, precision)) return rc;
+  OT_REQUIRE(qkv && out && dout && lse && dqkv && delta_ws, "ot_attn_bwd_masked: null operand");
+  if (B == 0) return OT_OK;
+  AttnArgs p{qkv, ld, H * head_dim, out, dout, nullptr, const_cast<float*>(lse), dqkv, delta_ws, B, H, I, K,
+             1.f / sqrtf((float)head_dim), qpos};
+  p.key_valid = key_valid;
+  p.ldv = ldv;
+  hipStream_t st = (hipStream_t)stream;
+  const int main_blocks = (int)ceil_div((int64_t)B * K * H * head_dim / 4, 256);
+  const int pad_blocks = (int)ceil_div((int64_t)B * H * (attn_kpad(K) - K), 256);
+  const int qpos_blocks = qpos ? (int)ceil_div((int64_t)B * attn_kpad(K), 256) : 0;
+  hipLaunchKernelGGL(attn_bwd_prep_kernel, dim3(main_blocks + pad_blocks + qpos_blocks), dim3(256), 0, st, out, dout,
+                     lse, delta_ws, B, H, K, head_dim, main_blocks, pad_blocks, qpos);
+  OT_LAUNCH_CHECK("ot_attn_bwd_masked(prep)");
+  const bool sel = qpos != nullptr;
+  if (K <= SMALL_K) {
+    OT_ATTN_MASKED_SMALL(attn_bwd_small_kernel, head_dim, K, dim3(ceil_div((int64_t)B * H, 4)), dim3(256), 0, st, p);
+  } else if (head_dim == 64) {
+    void (*kern)(AttnArgs) = sel ? attn_bwd_kernel<32, true, 2, false, true> : attn_bwd_kernel<32, false, 2, false, true>;
+    hipLaunchKernelGGL(kern, dim3((unsigned)((int64_t)B * H)), dim3(128), 0, st, p);
+  } else {
+    const int waves = head_dim >= 128 ? 2 : 4;
+    void (*kern)(AttnArgs) = nullptr;
+    switch (head_dim) {
+      case 16: kern = sel ? attn_bwd_kernel<16, true, 1, false, true> : attn_bwd_kernel<16, false, 1, false, true>; break;
+      case 32: kern = sel ? attn_bwd_kernel<32, true, 1, false, true> : attn_bwd_kernel<32, false, 1, false, true>; break;
+      default: kern = sel ? attn_bwd_kernel<128, true, 1, false, true> : attn_bwd_kernel<128, false, 1, false, true>; break;
+    }
+    hipLaunchKernelGGL(kern, dim3(ceil_div((int64_t)B * H, waves)), dim3(64 * waves), 0, st, p);
+  }
+  OT_LAUNCH_CHECK("ot_attn_bwd_masked");
+  return OT_OK;
+}
+
+extern "C" int ot_attn_fwd_cached_masked(const float* qkv, int64_t ld, const float* kv_cache, int64_t ldc,
+                                         const int32_t* req, int C, int H, int Ic, int n, int Kq, int head_dim,
+                                         const uint8_t* cache_valid, int64_t ldcv, float* out, float* lse_or_null,
+                                         void* stream) {
+  OT_REQUIRE(C >= 0 && H > 0 && Ic >= 0 && n > 0 && Kq > 0 && Kq <= n,
+             "ot_attn_fwd_cached_masked: bad sizes C=%d Ic=%d n=%d Kq=%d", C, Ic, n, Kq);
+  OT_REQUIRE(head_dim == 16 || head_dim == 32 || head_dim == 64 || head_dim == 128,
+             "ot_attn_fwd_cached_masked: head_dim %d unsupported", head_dim);
+  const int d = H * head_dim;
+  OT_REQUIRE(ld % 4 == 0 && ld >= 3 * d && (Ic == 0 || (ldc % 4 == 0 && ldc >= 2 * d)),
+             "ot_attn_fwd_cached_masked: ld/ldc must hold k|v and be multiples of 4");
+  OT_REQUIRE(qkv && out && req && (Ic == 0 || (kv_cache && cache_valid && ldcv >= Ic)),
+             "ot_attn_fwd_cached_masked: null operand or ldcv < Ic");
+  if (C == 0) return OT_OK;
+  AttnCachedArgs p{qkv, ld, kv_cache, kv_cache ? kv_cache + d : nullptr, ldc, req, out, C, H, Ic, n, Kq, d,
+                   1.f / sqrtf((float)head_dim), lse_or_null, cache_valid, ldcv};
+  const dim3 grid(ceil_div((int64_t)C * H, 4));
+  hipStream_t st = (hipStream_t)stream;
+  switch (head_dim) {
+    case 16: hipLaunchKernelGGL((attn_fwd_cached_kernel<16, true>), grid, dim3(256), 0, st, p); break;
+    case 32: hipLaunchKernelGGL((attn_fwd_cached_kernel<32, true>), grid, dim3(256), 0, st, p); break;
+    case 64: hipLaunchKernelGGL((attn_fwd_cached_kernel<64, true>), grid, dim3(256), 0, st, p); break;
+    default: hipLaunchKernelGGL((attn_fwd_cached_kernel<128, true>), grid, dim3(256), 0, st, p); break;
+  }
+  OT_LAUNCH_CHECK("ot_attn_fwd_cached_masked");
   return OT_OK;
 }

@@ -145,3 +145,70 @@ extern "C" int ot_seq_time_rows(const ot_seq_time* seqs, int nseq, int B, int L_
   OT_LAUNCH_CHECK("ot_seq_time_rows");
   return OT_OK;
 }
+
+// ------------------------------------------------------------------------------------------
+// Key-padding mask of layer 0 (include/onetrans_hip.h, "padding mask"): valid0[b][p] = 1 for [SEP] and NS tokens;
+// event j of sequence i (left-padded: its real events are the last len_i[b]) is valid iff j >= L_i - len_i[b], and
+// sits at its concatenation position off_i + j, or under time fusion at its rank in the time order (ot_seq_time_rows'
+// rank_out, indexed by the event's index in the concatenation of the sequences) — nothing is assumed about where
+// padding sorts.  One thread per (sample, concatenation position): the ranks are a permutation of the event
+// positions, so every byte of valid0 has one writer.  Lengths outside [0, L_i] are clamped here.
+namespace ot {
+
+struct SeqValidArgs {
+  int32_t L[SEQFUSE_MAX_SEQ], off[SEQFUSE_MAX_SEQ], start[SEQFUSE_MAX_SEQ];
+};
+
+__global__ __launch_bounds__(256) void seq_key_valid_kernel(SeqValidArgs a, int nseq, const int32_t* __restrict__ lens,
+                                                            int B, int L0, const int32_t* __restrict__ rank,
+                                                            int64_t ldr, uint8_t* __restrict__ valid0) {
+  const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (e >= (int64_t)B * L0) return;
+  const int b = (int)(e / L0), c = (int)(e % L0);
+  int pos = c;
+  uint8_t v = 1;
+  for (int i = 0; i < nseq; ++i) {
+    const int j = c - a.off[i];
+    if (j >= 0 && j < a.L[i]) {
+      int len = lens[(int64_t)i * B + b];
+      len = len < 0 ? 0 : (len > a.L[i] ? a.L[i] : len);
+      v = j >= a.L[i] - len;
+      if (rank) pos = rank[(int64_t)b * ldr + a.start[i] + j];
+      break;
+    }
+  }
+  if ((unsigned)pos < (unsigned)L0) valid0[(int64_t)b * L0 + pos] = v;   // (a rank outside the row is not written)
+}
+
+}  // namespace ot
+
+extern "C" int ot_seq_key_valid(const int32_t* lens, const int32_t* seq_len, const int32_t* seq_off, int nseq, int B,
+                                int L0, const int32_t* rank, int64_t ldr, uint8_t* valid0, void* stream) {
+  OT_REQUIRE(nseq >= 0 && nseq <= SEQFUSE_MAX_SEQ, "ot_seq_key_valid: nseq=%d out of range (0..%d)", nseq,
+             SEQFUSE_MAX_SEQ);
+  OT_REQUIRE(B >= 0 && L0 >= 1, "ot_seq_key_valid: bad sizes B=%d L0=%d", B, L0);
+  OT_REQUIRE(nseq == 0 || (seq_len && seq_off), "ot_seq_key_valid: null descriptors");
+  SeqValidArgs a{};
+  int64_t total = 0;
+  int prev_end = 0;
+  for (int i = 0; i < nseq; ++i) {
+    OT_REQUIRE(seq_len[i] >= 0 && seq_off[i] >= prev_end && (int64_t)seq_off[i] + seq_len[i] <= L0,
+               "ot_seq_key_valid: sequence %d: segment [%d, %d) overlaps its predecessor or leaves the %d tokens", i,
+               seq_off[i], seq_off[i] + seq_len[i], L0);
+    a.L[i] = seq_len[i];
+    a.off[i] = seq_off[i];
+    a.start[i] = (int32_t)total;
+    total += seq_len[i];
+    prev_end = seq_off[i] + seq_len[i];
+  }
+  // ranks permute the positions 0 .. total-1, so the event segments must be exactly those positions (no [SEP])
+  OT_REQUIRE(!rank || (ldr >= total && prev_end == total), "ot_seq_key_valid: ranks need ldr >= the %lld events and "
+             "segments without gaps", (long long)total);
+  if (B == 0) return OT_OK;
+  OT_REQUIRE(valid0 && (nseq == 0 || lens), "ot_seq_key_valid: null operand");
+  OT_REQUIRE((int64_t)B * L0 < ((int64_t)1 << 31) * 256, "ot_seq_key_valid: grid too large");
+  hipLaunchKernelGGL(seq_key_valid_kernel, dim3(ceil_div((int64_t)B * L0, 256)), dim3(256), 0, (hipStream_t)stream, a,
+                     nseq, lens, B, L0, rank, ldr, valid0);
+  OT_LAUNCH_CHECK("ot_seq_key_valid");
+  return OT_OK;
+}

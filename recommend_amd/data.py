@@ -20,6 +20,9 @@
   (int64 ``[B, cap]``, ``-1`` = empty slot; Zipf ids, lengths from 0 to cap) and, for every other 'sum' bag,
   per-slot weights ``name + '_weight'``; again from a generator of their own.
 
+* ``ragged_lengths`` — history lengths for ``config.seq_padding_mask`` (``name + config.seq_len_suffix``, int32
+  ``[B]``; empty and full histories both occur), for tests and tools/padmask_bench.py.  ``make_batch`` itself emits none.
+
 All generators are numpy ``Generator(PCG64)``: same seed => same batch, here and
 on the GPU box.
 """
@@ -65,6 +68,27 @@ def seq_times(seed: int, B: int, names: List[str], lens: List[int], suffix: str 
             i = rng.integers(0, L - 1, size=B)
             t[rows, i], t[rows, i + 1] = t[rows, i + 1].copy(), t[rows, i].copy()
         out[name + suffix] = (TIME_ORIGIN + t).astype(np.int64)
+    return out
+
+
+def ragged_lengths(B: int, config: OneTransConfig, seed: int = 1000, mean_fill: float = 0.5,
+                   seq_lens: Optional[List[int]] = None) -> Dict[str, np.ndarray]:
+    """Synthetic history lengths for ``seq_padding_mask``: {name + config.seq_len_suffix: int32 [B]} for every
+    configured sequence, binomial with mean ``mean_fill`` * L_name.  Sample 0 has empty histories and sample 1 (if any)
+    full ones; a generator of its own (seeded by ``seed``), so ``make_batch``'s arrays do not depend on it.  The real
+    events are the last ``len`` positions of ``make_batch``'s (full-length) sequences; what sits before them is padding
+    content, which the masked model must ignore."""
+    rng = np.random.Generator(np.random.PCG64([int(seed), 0x6C656E]))
+    names = config.feature_config['sequence_features']
+    caps = seq_lens or getattr(config, '_seq_lens', None) or [10] * len(names)
+    out = {}
+    for name, L in zip(names, caps):
+        lens = rng.binomial(int(L), min(1.0, max(0.0, float(mean_fill))), size=B)
+        if B > 0:
+            lens[0] = 0
+        if B > 1:
+            lens[1] = L
+        out[name + config.seq_len_suffix] = lens.astype(np.int32)
     return out
 
 

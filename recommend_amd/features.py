@@ -110,6 +110,7 @@ class SequenceProcessor:
         self.max_seq_len = config.max_seq_len
         self.width = width
         self.time_suffix = getattr(config, 'seq_time_suffix', '_time')
+        self.len_suffix = getattr(config, 'seq_len_suffix', '_len')
 
     def is_time_key(self, name: str, names) -> bool:
         """Is ``name`` the companion times of a sequence in ``names`` (``seq + seq_time_suffix``, the input of
@@ -125,6 +126,11 @@ class SequenceProcessor:
     def pad_times(self, seqs: Sequence[np.ndarray]) -> np.ndarray:
         """``pad_batch`` for event times: [B, max_seq_len] int64, left-padded with TIME_PAD."""
         return self.pad_batch(seqs, dtype=np.int64, pad_value=TIME_PAD, event_shape=())
+
+    def lengths(self, seqs: Sequence[np.ndarray]) -> np.ndarray:
+        """The number of real events ``pad_batch`` keeps of each sequence: min(len, max_seq_len), int32 [B] — the
+        ``name + seq_len_suffix`` input of ``seq_padding_mask`` (the real events are the last ``len`` positions)."""
+        return np.array([min(len(s), self.max_seq_len) for s in seqs], dtype=np.int32).reshape(len(seqs))
 
     def process_sequence(self, sequence_data: np.ndarray, sequence_type: Optional[str] = None) -> np.ndarray:
         """:75-94: keep the last max_seq_len events, left-pad with zeros (an empty sequence: float64
@@ -252,6 +258,10 @@ class OneTransDataset:
         sp = self.sequence_processor
         seq = {name: (sp.pad_times if sp.is_time_key(name, self.seq_data) else sp.pad_batch)([lst[i] for i in idx])
                for name, lst in self.seq_data.items()}
+        if getattr(self.config, 'seq_padding_mask', False):
+            # variable-length histories: each sequence's count of real events (its times share it)
+            seq.update({name + sp.len_suffix: sp.lengths([lst[i] for i in idx])
+                        for name, lst in self.seq_data.items() if not sp.is_time_key(name, self.seq_data)})
         lab = {t: np.asarray(v, dtype=np.float32)[idx].reshape(-1, 1) for t, v in self.labels.items()}
         return ns, seq, lab
 

@@ -478,6 +478,60 @@ def attn_bwd(qkv, ld, out, dout, lse, B, H, I, K, hd, dqkv, qpos=None, dq_part_b
         _probe.end('attention', 8.0 * (K * I - K * (K - 1) / 2) * hd * H * B, ev, f'bwd I{I} K{K} hd{hd}')
 
 
+def _valid_arg(valid):
+    """A key-padding mask argument (uint8 tensor, element offset, row stride) as (pointer, stride)."""
+    t, off, ldv = valid
+    if t.dtype != torch.uint8:
+        raise TypeError(f'key_valid: uint8 expected, got {t.dtype}')
+    return ptr((t, off)), ldv
+
+
+def attn_fwd_masked(qkv, ld, B, H, I, K, hd, out, lse, key_valid, qpos=None) -> None:
+    """ot_attn_fwd_masked: ot_attn_fwd under a key-padding mask.  ``key_valid`` = (uint8 tensor, element offset, row
+    stride): sample b's I bytes start at offset + b * stride (a layer's slice of layer 0's array)."""
+    kv, ldv = _valid_arg(key_valid)
+    ev = _probe.begin() if _probe is not None else None
+    call('ot_attn_fwd_masked', ptr(qkv), ld, B, H, I, K, ptr(qpos), hd, kv, ldv, ptr(out), ptr(lse), _prec(),
+         stream())
+    if ev is not None:
+        _probe.end('attention', 4.0 * (K * I - K * (K - 1) / 2) * hd * H * B, ev, f'fwd_masked I{I} K{K} hd{hd}')
+
+
+def attn_bwd_masked(qkv, ld, out, dout, lse, B, H, I, K, hd, dqkv, key_valid, qpos=None) -> None:
+    """ot_attn_bwd_masked: ot_attn_bwd under the forward's key-padding mask (float32 dqkv)."""
+    kv, ldv = _valid_arg(key_valid)
+    ws = workspace(size('ot_attn_bwd_workspace_size', B, H, K), qkv.device)
+    ev = _probe.begin() if _probe is not None else None
+    call('ot_attn_bwd_masked', ptr(qkv), ld, ptr(out), ptr(dout), ptr(lse), B, H, I, K, ptr(qpos), hd, kv, ldv,
+         ptr(dqkv), ptr(ws), _prec(), stream())
+    if ev is not None:
+        _probe.end('attention', 8.0 * (K * I - K * (K - 1) / 2) * hd * H * B, ev, f'bwd_masked I{I} K{K} hd{hd}')
+
+
+def attn_fwd_cached_masked(qkv, ld, kv_cache, ldc, req, C, H, Ic, n, Kq, hd, out, cache_valid, lse=None) -> None:
+    """ot_attn_fwd_cached_masked: ot_attn_fwd_cached (with ``lse``: ot_attn_fwd_cached_lse) with a key-padding mask
+    over the cached rows, ``cache_valid`` = (uint8 tensor, element offset, row stride) or None when Ic == 0."""
+    cv, ldcv = _valid_arg(cache_valid) if cache_valid is not None else (None, 0)
+    ev = _probe.begin() if _probe is not None else None
+    call('ot_attn_fwd_cached_masked', ptr(qkv), ld, ptr(kv_cache), ldc, ptr(req), C, H, Ic, n, Kq, hd, cv, ldcv,
+         ptr(out), ptr(lse), stream())
+    if ev is not None:
+        _probe.end('attention', 4.0 * (Kq * (Ic + n) - Kq * (Kq - 1) / 2) * hd * H * C, ev,
+                   f'fwd_cached_masked Ic{Ic} n{n} K{Kq} hd{hd}')
+
+
+def seq_key_valid(lens, seq_len, seq_off, B: int, L0: int, valid0, rank=None) -> None:
+    """ot_seq_key_valid: layer 0's key-padding mask valid0 [B, L0] (uint8) from the present sequences' lengths
+    ``lens`` (device int32 [nseq, B]), their caps ``seq_len`` and first token positions ``seq_off`` (host ints), and
+    under time fusion the events' ranks ``rank`` [B, L_S] (seq_time_rows' rank_out)."""
+    n = len(seq_len)
+    arr = ctypes.c_int32 * max(1, n)
+    sl, so = arr(*seq_len), arr(*seq_off)               # (read by the call itself: host descriptors)
+    call('ot_seq_key_valid', ptr(lens), ctypes.cast(sl, ctypes.c_void_p), ctypes.cast(so, ctypes.c_void_p), n, B, L0,
+         ptr(rank),
+         rank.shape[1] if rank is not None else 0, ptr(valid0), stream())
+
+
 def attn_fwd_cached(qkv, ld, kv_cache, ldc, req, C, H, Ic, n, Kq, hd, out, lse=None) -> None:
     """ot_attn_fwd_cached: N-side queries over a request's cached S-side K/V plus their own rows; given ``lse``
     [C, H, Kq], ot_attn_fwd_cached_lse: the same forward, which also writes lse for the backward."""

@@ -30,7 +30,8 @@ from . import kernels as K
 from ._lib import (OT_AX_BF16, OT_AX_BF16_RMSNORM, OT_AX_GELU, OT_AX_RMSNORM, OT_EPI_ACCUMULATE, OT_EPI_AUX_BF16, OT_EPI_BIAS,
                    OT_EPI_C_BF16, OT_EPI_DROPOUT, OT_EPI_GELU_BWD, OT_EPI_RESIDUAL, OT_EPI_RMSNORM_BWD,
                    OT_EPI_ROW_RSTD, OT_EPI_ROWDOT, OT_GEMM_NN, OT_GEMM_NT, OT_WG_D_BF16, NS_FIELD_BYTES)
-from .config import OneTransConfig, check_bag_features, check_pyramid_select, check_seq_fusion, get_model_config
+from .config import (OneTransConfig, check_bag_features, check_padding_mask, check_pyramid_select, check_seq_fusion,
+                     get_model_config)
 from .layout import TILE, FlatLayout, RowMap, build_map, head_map, identity_map, layer_maps, round_up
 from .params import init_params, ns_table_offsets
 
@@ -169,6 +170,13 @@ def layer_seed(seed: int, b0: int, I: int, d: int) -> int:
     return (seed + b0 * I * d * 0x9E3779B1) & 0xFFFFFFFF if b0 else seed
 
 
+def _layer_valid(kvalid, I):
+    """The slice of layer 0's key-padding mask [B, L0] that a layer of I tokens reads under the tail keep: its last I
+    columns, as (tensor, element offset, row stride) — the same array, no copy."""
+    L0 = kvalid.shape[1]
+    return kvalid, L0 - I, L0
+
+
 def _attn_qpos(cfg, pos):
     """Kept-query positions for the attention kernels: None (the tail rule, I - K + j) when the keep is
     the reference's tail — ot_pyramid_select returns exactly that set there, in order."""
@@ -207,11 +215,12 @@ def a_row_bounds(on: bool, x, ld: int, rows: int, n: int, reported=None) -> Dict
 
 
 def _block_forward(m, l, x, I, Kq, seed, training, rstd_in=None, select=False, need_out=True, need_u=True,
-                   bounds=None):
+                   bounds=None, kvalid=None):
     """The block's forward kernels (``_Block.forward``; also the backward's recompute with
     ``need_out=False``, which stops after FFN1: the backward needs u, not the block output).
     ``need_u=False`` (no backward will read this call's u): the fused FFN forward does not write it (saved u None).
     ``bounds``: this forward's PairBounds or None.
+    ``kvalid``: layer 0's key-padding mask [B, L0] (uint8; seq_padding_mask) or None; the layer reads its last I columns.
     Returns (x2, rstd_out, saved, pos, inv, rate); saved = (x, rstd1, qkv, o, lse, x1, rstd2, u, h, xn1, x1n);
     h = the stored bf16 gelu(u), xn1 / x1n = the bf16 normalised QKV / FFN1 inputs (bf16 mode) or None."""
     cfg = m.config
@@ -300,10 +309,15 @@ def _block_forward(m, l, x, I, Kq, seed, training, rstd_in=None, select=False, n
     out = (lambda name: bounds.out(l, name)) if bounds is not None else (lambda name: None)
     # the Wo forward on the fp16 pair (pair-form Wo image): O's row maxima, per head, and |O| from the slice forward
     pwo_f = m.gemm_pair(f'blk.{l}.wo', 'fwd')
-    o_rep = not m.attn_fp8 and K.attn_amax_supported(I, Kq, hd, qp_f)
+    # (the masked attention reports no bounds: O's row maxima then come from a_row_bounds' own pass, and the Wo weight
+    # gradient, without |O|, runs the exact split)
+    o_rep = kvalid is None and not m.attn_fp8 and K.attn_amax_supported(I, Kq, hd, qp_f)
     rm_o = torch.empty(B * Kq, H, device=dev) if pwo_f and o_rep else None
-    K.attn_fwd(qkv, 3 * d, B, H, I, Kq, hd, o, lse, qpos=qp_f, fp8=m.attn_fp8, dequant=m.attn_fp8 and training,
-               fp8_terms=m.fp8_terms, deq16=qkv16, amax=out('o') if o_rep else None, rowmax=rm_o)
+    if kvalid is not None:
+        K.attn_fwd_masked(qkv, 3 * d, B, H, I, Kq, hd, o, lse, _layer_valid(kvalid, I), qpos=qp_f)
+    else:
+        K.attn_fwd(qkv, 3 * d, B, H, I, Kq, hd, o, lse, qpos=qp_f, fp8=m.attn_fp8, dequant=m.attn_fp8 and training,
+                   fp8_terms=m.fp8_terms, deq16=qkv16, amax=out('o') if o_rep else None, rowmax=rm_o)
     pa_o = a_row_bounds(pwo_f, o, d, B * Kq, d, rm_o)
     if qkv16 is not None:
         qkv = qkv16
@@ -419,12 +433,12 @@ class _Block(torch.autograd.Function):
     of the next: ``rstd_in``), and the FFN1 / QKV dgrad epilogues apply the norm backward."""
 
     @staticmethod
-    def forward(ctx, flat, x, m, l, I, Kq, seed, training, rstd_in=None, select=False, bounds=None):
+    def forward(ctx, flat, x, m, l, I, Kq, seed, training, rstd_in=None, select=False, bounds=None, kvalid=None):
         # u is read by a backward only: with the recompute (which forms it again) or no input that needs a gradient
         # (inference) this forward need not write it
         x2, rstd_out, saved, pos, inv, rate = _block_forward(
             m, l, x, I, Kq, seed, training, rstd_in, select, bounds=bounds,
-            need_u=not m.recompute and any(ctx.needs_input_grad))
+            need_u=not m.recompute and any(ctx.needs_input_grad), kvalid=kvalid)
         if m.recompute:
             # activation recompute: keep the block input (and its rstd); the backward re-runs the
             # forward kernels up to FFN1 (dropout masks and pyramid keeps are deterministic)
@@ -433,7 +447,7 @@ class _Block(torch.autograd.Function):
         else:
             ctx.save_for_backward(*saved)
         ctx.m, ctx.l, ctx.I, ctx.Kq, ctx.seed, ctx.rate = m, l, I, Kq, seed, rate
-        ctx.pos, ctx.inv, ctx.bounds = pos, inv, bounds
+        ctx.pos, ctx.inv, ctx.bounds, ctx.kvalid = pos, inv, bounds, kvalid
         if rstd_out is None:
             rstd_out = x2.new_empty(0)          # not fused: the next block computes its own rstd
         ctx.mark_non_differentiable(rstd_out)
@@ -448,12 +462,12 @@ class _Block(torch.autograd.Function):
     @staticmethod
     def _backward(ctx, dx2, _drstd=None):
         m, l, I, Kq, seed, rate = ctx.m, ctx.l, ctx.I, ctx.Kq, ctx.seed, ctx.rate
-        pos, inv, bounds = ctx.pos, ctx.inv, ctx.bounds
+        pos, inv, bounds, kvalid = ctx.pos, ctx.inv, ctx.bounds, ctx.kvalid
         if m.recompute:
             xin, rstd_in = ctx.saved_tensors
             training, select = ctx.fwd_args
             _, _, saved, pos, inv, _ = _block_forward(m, l, xin, I, Kq, seed, training, rstd_in, select,
-                                                      need_out=False, bounds=bounds)
+                                                      need_out=False, bounds=bounds, kvalid=kvalid)
             x, rstd1, qkv, o, lse, x1, rstd2, u, h, xn1, x1n = saved
         else:
             x, rstd1, qkv, o, lse, x1, rstd2, u, h, xn1, x1n = ctx.saved_tensors
@@ -582,13 +596,17 @@ class _Block(torch.autograd.Function):
         dqkv = torch.empty(B * I, 3 * d, device=dev, dtype=torch.int16 if dq_bf else torch.float32)
         if Kq < I:
             dqkv[:, :d].zero_()
-        bwd_b = not dq_bf and K.attn_amax_supported(I, Kq, hd, qp, backward=True)
+        bwd_b = kvalid is None and not dq_bf and K.attn_amax_supported(I, Kq, hd, qp, backward=True)
         b_dq = out('dqkv') if bwd_b else None
         # the QKV dgrad on the fp16 pair: dQKV's row maxima [row][q / k / v][head] from the attention backward (the
         # dQ part of rows without a query stays 0), else the row-absmax pass
         pqkv = m.dgrad_pair(f'blk.{l}.wqkv')
         rm_dq = torch.zeros(B * I, 3 * H, device=dev) if pqkv and bwd_b else None
-        K.attn_bwd(qkv, 3 * d, o, do, lse, B, H, I, Kq, hd, dqkv, qpos=qp, dq_part_bf16=True, amax=b_dq, rowmax=rm_dq)
+        if kvalid is not None:
+            K.attn_bwd_masked(qkv, 3 * d, o, do, lse, B, H, I, Kq, hd, dqkv, _layer_valid(kvalid, I), qpos=qp)
+        else:
+            K.attn_bwd(qkv, 3 * d, o, do, lse, B, H, I, Kq, hd, dqkv, qpos=qp, dq_part_bf16=True, amax=b_dq,
+                       rowmax=rm_dq)
         pa_q = a_row_bounds(pqkv, dqkv, 3 * d, B * I, 3 * d, rm_dq)
         an1 = xn1 is not None and dq_bf
         with m.side(xn1 if an1 else x, dqkv, rstd1, *keep):
@@ -617,7 +635,7 @@ class _Block(torch.autograd.Function):
         m.side_block_done()
         if m.grad_ready is not None:
             m.grad_ready(l)                     # this block's banks are final: the DP exchange may start
-        return None, dx, None, None, None, None, None, None, None, None, None
+        return None, dx, None, None, None, None, None, None, None, None, None, None
 
 
 def _wgrad_single(m, A, D, K_, N, mt, dW, acc, dev, mrows=0, rowmap=None, a_bound=None, d_bound=None):
@@ -792,6 +810,8 @@ class OneTransModel(nn.Module):
         check_pyramid_select(cfg)
         check_seq_fusion(cfg)
         check_bag_features(cfg)
+        check_padding_mask(cfg)
+        self.padding_mask = bool(getattr(cfg, 'seq_padding_mask', False))
         self.time_fusion = getattr(cfg, 'seq_fusion', 'sep') == 'time'
         # compute_dtype (build knob): 'fp32' (the reference's arithmetic: split or f32 GEMMs, ``matmul`` below),
         # 'bf16', or 'fp8attn' = BASELINE configs[4]'s attention on
@@ -1117,6 +1137,7 @@ class OneTransModel(nn.Module):
         key = (B, tuple(present), ns_present, id_seq) + ((tuple((n, cap, w is not None) for n, cap, _, w in bags),)
                                                          if bags else ())
         times = self._seq_times(seq, present, B) if self.time_fusion and present else None
+        lens = self._seq_lengths(seq, present, B) if self.padding_mask else None
         plan = self._plans.get(key)
         if plan is None:
             plan = self._build_plan(B, present, ns_present, id_seq, bags)
@@ -1145,6 +1166,8 @@ class OneTransModel(nn.Module):
                     buf.copy_(t)
                 K.seq_time_rows(plan['time_descs'], len(present), B, plan['L_S'], plan['L0'], plan['seq_rows_t'],
                                 rank_out=plan['seq_rank'], last_time=plan['last_time'], device=dev)
+            if self.padding_mask:
+                self._stage_valid(plan, lens, B)
             if id_seq and 'emb.seq_item' in self.sharded:
                 # row-sharded table: the rows arrive through the all-to-all lookup in token order, and
                 # the projection reads them through the static (identity) row map; the ids are staged
@@ -1178,7 +1201,47 @@ class OneTransModel(nn.Module):
                     o += B * L
                 plan['seq_A'] = buf
                 plan['seq_ids'] = None
+        if self.padding_mask and plan['seq_map'] is None:
+            self._stage_valid(plan, [], B)             # no sequence present: every token is valid
         return plan
+
+    def _seq_lengths(self, seq, present, B) -> List[torch.Tensor]:
+        """The present sequences' real-event counts (``seq_padding_mask``): ``seq[name + seq_len_suffix]``, an integer
+        [B] or [B, 1] host array or device tensor each.  A host array is range-checked here; a device tensor is not read
+        back (ot_seq_key_valid clamps it)."""
+        sfx = self.config.seq_len_suffix
+        out = []
+        for (_, n, L) in present:
+            if n + sfx not in seq:
+                raise ValueError(f'seq_padding_mask: sequence {n!r} has no lengths ({n + sfx!r} is missing from '
+                                 'seq_features)')
+            t = seq[n + sfx]
+            t = t if isinstance(t, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(t))
+            if t.is_floating_point() or t.is_complex() or t.dtype == torch.bool:
+                raise TypeError(f'seq_padding_mask: the lengths of sequence {n!r} ({n + sfx!r}) are {t.dtype}; '
+                                'integers are expected')
+            if tuple(t.shape) not in ((B,), (B, 1)):
+                raise ValueError(f'seq_padding_mask: the lengths of sequence {n!r} ({n + sfx!r}) have shape '
+                                 f'{tuple(t.shape)}, expected {(B,)} or {(B, 1)}')
+            if t.device.type == 'cpu' and B and (int(t.min()) < 0 or int(t.max()) > L):
+                raise ValueError(f'seq_padding_mask: the lengths of sequence {n!r} ({n + sfx!r}) leave [0, {L}]')
+            out.append(t.reshape(B))
+        return out
+
+    def _stage_valid(self, plan, lens, B) -> None:
+        """Layer 0's key-padding mask of this call, plan['valid0'] [B, L0] uint8: the lengths staged into the plan's
+        buffer, then one ot_seq_key_valid launch (after ot_seq_time_rows under time fusion: it reads the ranks).  A
+        fresh array per call — the backward of this forward keeps reading it after a later forward restaged the plan."""
+        dev = self.device
+        groups = plan.get('seq_groups', []) if lens else []
+        if lens:
+            buf = plan['len_buf']
+            for k, (t, (_, _, L)) in enumerate(zip(lens, groups)):
+                buf[k].copy_(t.clamp(0, L))             # (before the narrowing to int32; no read-back)
+        valid0 = torch.empty(B, plan['L0'], dtype=torch.uint8, device=dev)
+        K.seq_key_valid(plan['len_buf'] if lens else None, [L for (_, _, L) in groups], [p0 for (_, p0, _) in groups],
+                        B, plan['L0'], valid0, rank=plan.get('seq_rank') if lens else None)
+        plan['valid0'] = valid0
 
     def _bag_inputs(self, ns, ns_present, B):
         """The present bag features' inputs as (name, cap, ids [B, cap], weights [B, cap] or None): integer ids, and
@@ -1281,6 +1344,9 @@ class OneTransModel(nn.Module):
             plan['seq_seg_off'] = offs
             seq_in = torch.from_numpy(rm.rows[2].copy()).to(dev)
             plan['seq_in'] = seq_in
+            if self.padding_mask:
+                plan['seq_groups'] = seq_groups
+                plan['len_buf'] = torch.zeros(len(seq_groups), B, dtype=torch.int32, device=dev)
             if not id_seq:
                 plan['seq_buf'] = torch.empty(cmp_off, cfg.seq_feature_dim, device=dev)
             if self.time_fusion:
@@ -1402,7 +1468,7 @@ class OneTransModel(nn.Module):
             Kq = s['keep'] if l < nl - 1 else 1
             select = l < nl - 1 and Kq < s['in_len']         # a pyramid keep (the last layer: DCE, tail)
             x, rstd = _Block.apply(self.flat, x, self, l, s['in_len'], Kq, layer_seed(seed, b0, s['in_len'],
-                                   self.config.hidden_dim), training, rstd, select, bounds)
+                                   self.config.hidden_dim), training, rstd, select, bounds, plan.get('valid0'))
         probs, logits = _Head.apply(self.flat, x, self)
         probs._ot_logits = logits            # keras_bce_loss takes the BCE from the logits (Keras _keras_logits)
         return probs

@@ -49,6 +49,9 @@ def check_supported(m) -> None:
                                   'attention backward is native f32)')
     if m.recompute:
         raise NotImplementedError('forward_requests: recompute_blocks is not supported')
+    if getattr(m, 'padding_mask', False):
+        raise NotImplementedError('forward_requests: seq_padding_mask is not supported (the cached attention backward, '
+                                  'ot_attn_bwd_cached, carries no padding mask)')
     if m.sharded:
         raise NotImplementedError('forward_requests: a row-sharded table is not supported')
     import torch.distributed as dist

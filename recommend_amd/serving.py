@@ -33,6 +33,7 @@ from __future__ import annotations
 
 from typing import Dict, List, Optional
 
+import numpy as np
 import torch
 
 from . import kernels as K
@@ -40,12 +41,21 @@ from ._lib import OneTransHipError
 from .span_block import check_req, request_schedule, s_rows, span_forward
 
 
+def _cache_valid(valid, L_S: int, s: int):
+    """The key-padding mask of a layer's s S rows — the last s of the L_S columns of ``valid`` [R, L_S] (tail keep) — as
+    the kernels take it (tensor, element offset, row stride), or None without a mask."""
+    return None if valid is None else (valid, L_S - s, L_S)
+
+
 class RequestCache:
     """Stage-I output for R requests: per layer the S-side qkv rows [R*Ic, 3d] (k at col d, v at 2d)
     and Ic, the number of S tokens in that layer's input."""
 
-    def __init__(self, R: int, L_S: int, layers: List[Dict], present=(), last_time: Optional[torch.Tensor] = None):
+    def __init__(self, R: int, L_S: int, layers: List[Dict], present=(), last_time: Optional[torch.Tensor] = None,
+                 valid: Optional[torch.Tensor] = None):
         self.R, self.L_S, self.layers = R, L_S, layers
+        # seq_padding_mask: the S tokens' validity, uint8 [R, L_S]; a layer with Ic cached rows reads its last Ic columns
+        self.valid = valid
         self.present = tuple(present)          # sequence names present in the requests, config order
         # seq_fusion='time': each request's latest event time, [R] int64 on the device (ot_seq_time_rows);
         # extend_requests appends only events after it
@@ -87,17 +97,20 @@ class OneTransServer:
         plan = m._plan({}, seq_features)
         R, L_S = plan['B'], plan['L_S']
         x = s_rows(_Tokenize.apply(m.flat, m, plan), plan)                # NS rows zero (no NS features)
+        # seq_padding_mask: the S columns of the plan's validity array (its lengths come with seq_features)
+        valid = plan['valid0'][:, :L_S].contiguous() if m.padding_mask else None
         layers = []
         for l, e in enumerate(self.schedule(L_S)):
             s, kS = e['s'], e['kS']
             if s == 0:
                 layers.append({'Ic': 0, 'kv': None})
                 continue
-            x, qkv, _ = span_forward(m, l, x, R, s, kS, 0, e['I'], cached=False)     # S queries see S keys only
+            x, qkv, _ = span_forward(m, l, x, R, s, kS, 0, e['I'], cached=False,     # S queries see S keys only
+                                     valid=_cache_valid(valid, L_S, s))
             layers.append({'Ic': s, 'kv': qkv})
         present = [n for n in cfg.feature_config['sequence_features'] if n in seq_features]
         last_time = plan['last_time'].clone() if m.time_fusion else None
-        return RequestCache(R, L_S, layers, present, last_time)
+        return RequestCache(R, L_S, layers, present, last_time, valid)
 
     # ------------------------------------------------------------------ cross-request append
     @torch.no_grad()
@@ -140,6 +153,13 @@ class OneTransServer:
         feats = {seq_name: new_events}
         if m.time_fusion:
             feats[seq_name + cfg.seq_time_suffix] = self._check_new_times(cache, seq_name, new_events, new_times)
+        if m.padding_mask:
+            # appended events are real: their span is all valid, and it attends over the cache under the cache's mask
+            if cache.valid is None:
+                raise ValueError('extend_requests: the request cache holds no validity (it was not encoded under '
+                                 'seq_padding_mask)')
+            ev = torch.as_tensor(new_events)
+            feats[seq_name + cfg.seq_len_suffix] = np.full(ev.shape[0], ev.shape[1], dtype=np.int32)
         plan = m._plan({}, feats)
         if plan['B'] != R:
             raise ValueError(f'extend_requests: {plan["B"]} rows of new events for {R} cached requests')
@@ -155,10 +175,13 @@ class OneTransServer:
             lay = cache.layers[l]
             keep = e_new['kS'] - e_old['kS']                              # new S rows kept by this layer
             x, qkv, _ = span_forward(m, l, x, R, dL, dL if keep == dL else 0, Ic, e_new['I'], cached=True,
-                                     kv=lay['kv'] if Ic > 0 else None, req=req, R=R)
+                                     kv=lay['kv'] if Ic > 0 else None, req=req, R=R,
+                                     valid=_cache_valid(cache.valid, cache.L_S, Ic))
             kv = qkv if Ic == 0 else torch.cat([lay['kv'].view(R, Ic, 3 * d), qkv.view(R, dL, 3 * d)], 1)
             layers.append({'Ic': Ic + dL, 'kv': kv.reshape(R * (Ic + dL), 3 * d)})
-        return RequestCache(R, cache.L_S + dL, layers, cache.present, last_time)
+        valid = (torch.cat([cache.valid, torch.ones(R, dL, dtype=torch.uint8, device=m.device)], 1)
+                 if m.padding_mask else None)
+        return RequestCache(R, cache.L_S + dL, layers, cache.present, last_time, valid)
 
     def _check_new_times(self, cache: RequestCache, seq_name: str, new_events, new_times) -> torch.Tensor:
         """``extend_requests`` under seq_fusion='time': the new events' times as a device int64 [R, dL] tensor,
@@ -195,6 +218,8 @@ class OneTransServer:
         m = self.m
         plan = m._plan(non_seq_features, {})
         C = plan['B']
+        if m.padding_mask and cache.valid is None:
+            raise ValueError(f'{who}: the request cache holds no validity (it was not encoded under seq_padding_mask)')
         check_req(who, req, cache.R, C, ordered=False)
         req = torch.as_tensor(req).to(m.device, torch.int32).contiguous()
         x = _Tokenize.apply(m.flat, m, plan)                              # [C*L_NS, d]: NS tokens only
@@ -204,7 +229,7 @@ class OneTransServer:
             if lay['Ic'] != s:
                 raise OneTransHipError(f'{who}: request cache does not match the schedule')
             x, _, _ = span_forward(m, l, x, C, n, kN, s, e['I'], cached=True, kv=lay['kv'] if s > 0 else None,
-                                   req=req, R=cache.R)
+                                   req=req, R=cache.R, valid=_cache_valid(cache.valid, cache.L_S, s))
         probs, _ = _Head.apply(m.flat, x, m)                               # [T, C]
         return probs, req
 
@@ -304,6 +329,10 @@ class OneTransInferenceEngine:
         # events sort first in the time-ordered stream
         seq = {k: sp.process_times(v) if sp.is_time_key(k, sequence_features) else sp.process_sequence(np.asarray(v))
                for k, v in sequence_features.items()}
+        if getattr(self.config, 'seq_padding_mask', False):
+            # variable-length histories: the number of real events process_sequence kept (the last ``len`` positions)
+            seq.update({k + sp.len_suffix: sp.lengths([np.asarray(v)])[0] for k, v in sequence_features.items()
+                        if not sp.is_time_key(k, sequence_features)})
         return non_seq, seq
 
     def _is_bag(self, name: str) -> bool:

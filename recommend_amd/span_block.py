@@ -67,7 +67,8 @@ def check_req(who: str, req, R: int, C: int, ordered: bool) -> None:
 
 
 def span_forward(m, l: int, x: torch.Tensor, B: int, I: int, Kq: int, p0: int, I_full: int, *, cached: bool,
-                 kv=None, req=None, R: int = 0, seed: int = 0, rate: float = 0.0, for_backward: bool = False):
+                 kv=None, req=None, R: int = 0, seed: int = 0, rate: float = 0.0, for_backward: bool = False,
+                 valid=None):
     """OneTransBlock.call (model.py:186-200) on B spans of I rows (positions p0.. of a layer of I_full tokens),
     keeping the last Kq; plain kernel forms.  Returns (x2 [B*Kq, d], qkv [B*I, 3d], saved); Kq = 0: only the K/V
     rows of qkv are produced and x2 is None.
@@ -77,7 +78,9 @@ def span_forward(m, l: int, x: torch.Tensor, B: int, I: int, Kq: int, p0: int, I
     ``rate`` > 0: dropout on the two branch outputs under ``seed``, sites 2l and 2l+1.
     ``for_backward``: the forward of a training step: the Q columns of rows without a query are zeroed (the
     backward's weight gradient reads every column), the cached attention writes its lse, and ``saved`` is what the
-    backward reads (x, rstd1[, qkv, o, lse, x1, rstd2, u])."""
+    backward reads (x, rstd1[, qkv, o, lse, x1, rstd2, u]).
+    ``valid`` (seq_padding_mask): the key-padding mask as (uint8 tensor, element offset, row stride) — of the span's
+    own I keys when not ``cached``, of the Ic cached rows ([R, .]) when ``cached`` (the span's own rows are valid)."""
     cfg = m.config
     d, f, H = cfg.hidden_dim, cfg.ffn_dim, cfg.num_heads
     hd = d // H
@@ -106,7 +109,13 @@ def span_forward(m, l: int, x: torch.Tensor, B: int, I: int, Kq: int, p0: int, I
     lse = torch.empty(B * H * Kq, device=dev) if for_backward or not cached else None
     if cached:
         Ic = kv.shape[0] // R if kv is not None else 0
-        K.attn_fwd_cached(qkv, 3 * d, (kv, d) if kv is not None else None, 3 * d, req, B, H, Ic, I, Kq, hd, o, lse)
+        if valid is not None:
+            K.attn_fwd_cached_masked(qkv, 3 * d, (kv, d) if kv is not None else None, 3 * d, req, B, H, Ic, I, Kq, hd,
+                                     o, valid if Ic > 0 else None, lse)
+        else:
+            K.attn_fwd_cached(qkv, 3 * d, (kv, d) if kv is not None else None, 3 * d, req, B, H, Ic, I, Kq, hd, o, lse)
+    elif valid is not None:
+        K.attn_fwd_masked(qkv, 3 * d, B, H, I, Kq, hd, o, lse, valid)
     else:
         K.attn_fwd(qkv, 3 * d, B, H, I, Kq, hd, o, lse)
     # x1 = x[tail] + drop(o @ Wo)
