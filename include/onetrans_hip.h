@@ -481,6 +481,24 @@ int ot_attn_fwd_cached_masked(const float* qkv, int64_t ld, const float* kv_cach
 int ot_seq_key_valid(const int32_t* lens, const int32_t* seq_len, const int32_t* seq_off, int nseq, int B, int L0,
                      const int32_t* rank, int64_t ldr, uint8_t* valid0, void* stream);
 
+/* ---- bf16 request cache for serving (attention_kv16.hip) -----------------------------------
+ * The cached S-side K/V rows of a request, stored rounded to bf16 (round to nearest even, NaN stays NaN, a value
+ * past the bf16 range becomes +-inf) in rows of ldc16 elements (ldc16 % 8 == 0, >= 2d: K at col 0, V at col d),
+ * request r owning rows [r*req_stride, (r+1)*req_stride).  Rounding happens only when a row is stored; the
+ * attention widens the rows in registers and computes in f32, a candidate's own rows stay f32.
+ *
+ * ot_kv_pack_bf16: K | V columns [d, 3d) of qkv row r*rows_per_req + i -> row r*req_stride + row0 + i, cols
+ * [0, 2d) of kv16 (r < R, i < rows_per_req; d % 4 == 0, req_stride >= row0 + rows_per_req).  One pass, 16-byte
+ * loads and stores; columns >= 2d and rows outside [row0, row0 + rows_per_req) of each request are not written.
+ * ot_attn_fwd_cached_kv16: ot_attn_fwd_cached_masked over such a cache: request r's key j (j < Ic <= req_stride) is
+ * kv16 row r*req_stride + j.  cache_valid NULL = every cached row valid.  Same out / lse convention.
+ * qkv, kv16 and out are 16-byte aligned.  R == 0 / C == 0 return OT_OK without a launch. */
+int ot_kv_pack_bf16(const float* qkv, int64_t ld, int R, int64_t rows_per_req, int d, uint16_t* kv16, int64_t ldc16,
+                    int64_t req_stride, int64_t row0, void* stream);
+int ot_attn_fwd_cached_kv16(const float* qkv, int64_t ld, const uint16_t* kv16, int64_t ldc16, int64_t req_stride,
+                            const int32_t* req, int C, int H, int Ic, int n, int Kq, int head_dim,
+                            const uint8_t* cache_valid, int64_t ldcv, float* out, float* lse_or_null, void* stream);
+
 /* ---- pyramid query selection (pyramid.hip) -----------------------------------------------
  * Replaces PyramidScheduler.get_layer_config + tf.gather (model.py:287-302, 356, 371): per sample,
  * keep the K of I tokens with the largest key (score[b*I+p] * score_sign, ties to the later

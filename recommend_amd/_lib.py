@@ -207,6 +207,9 @@ SIGNATURES = {
     'ot_attn_fwd_cached_masked': (c_int, [P, I64, P, I64, P, c_int, c_int, c_int, c_int, c_int, c_int, P, I64, P, P,
                                           P]),
     'ot_seq_key_valid': (c_int, [P, P, P, c_int, c_int, c_int, P, I64, P, P]),
+    'ot_kv_pack_bf16': (c_int, [P, I64, c_int, I64, c_int, P, I64, I64, I64, P]),
+    'ot_attn_fwd_cached_kv16': (c_int, [P, I64, P, I64, I64, P, c_int, c_int, c_int, c_int, c_int, c_int, P, I64, P, P,
+                                        P]),
     'ot_ns_bag_pool': (c_int, [P, c_int, c_int, P, I64, P, P]),
     'ot_ns_bag_grad_pack': (c_int, [P, c_int, c_int, P, I64, P, P, P, P]),
 }

@@ -520,6 +520,32 @@ def attn_fwd_cached_masked(qkv, ld, kv_cache, ldc, req, C, H, Ic, n, Kq, hd, out
                    f'fwd_cached_masked Ic{Ic} n{n} K{Kq} hd{hd}')
 
 
+def kv_pack_bf16(qkv, ld, R, rows_per_req, d, kv16, ldc16, req_stride, row0) -> None:
+    """ot_kv_pack_bf16: the K | V columns of ``qkv``'s R * rows_per_req rows, rounded to bf16, into rows
+    row0 .. row0 + rows_per_req - 1 of every request of the bf16 cache ``kv16`` (req_stride rows of ldc16 each)."""
+    if kv16.dtype != torch.bfloat16:
+        raise TypeError(f'kv_pack_bf16: a bfloat16 cache is expected, got {kv16.dtype}')
+    ev = _probe.begin() if _probe is not None else None
+    call('ot_kv_pack_bf16', ptr(qkv), ld, R, rows_per_req, d, ptr(kv16), ldc16, req_stride, row0, stream())
+    if ev is not None:
+        _probe.end('rowwise', 0.0, ev, f'kv_pack_bf16 R{R} rows{rows_per_req} d{d}')
+
+
+def attn_fwd_cached_kv16(qkv, ld, kv16, ldc16, req_stride, req, C, H, Ic, n, Kq, hd, out, cache_valid=None,
+                         lse=None) -> None:
+    """ot_attn_fwd_cached_kv16: ot_attn_fwd_cached_masked over a bf16 cache (request r's key j = row
+    r * req_stride + j of ``kv16``, K at col 0, V at col d); ``cache_valid`` None = every cached row valid."""
+    if kv16 is not None and kv16.dtype != torch.bfloat16:
+        raise TypeError(f'attn_fwd_cached_kv16: a bfloat16 cache is expected, got {kv16.dtype}')
+    cv, ldcv = _valid_arg(cache_valid) if cache_valid is not None else (None, 0)
+    ev = _probe.begin() if _probe is not None else None
+    call('ot_attn_fwd_cached_kv16', ptr(qkv), ld, ptr(kv16), ldc16, req_stride, ptr(req), C, H, Ic, n, Kq, hd, cv,
+         ldcv, ptr(out), ptr(lse), stream())
+    if ev is not None:
+        _probe.end('attention', 4.0 * (Kq * (Ic + n) - Kq * (Kq - 1) / 2) * hd * H * C, ev,
+                   f'fwd_cached_kv16 Ic{Ic} n{n} K{Kq} hd{hd}')
+
+
 def seq_key_valid(lens, seq_len, seq_off, B: int, L0: int, valid0, rank=None) -> None:
     """ot_seq_key_valid: layer 0's key-padding mask valid0 [B, L0] (uint8) from the present sequences' lengths
     ``lens`` (device int32 [nseq, B]), their caps ``seq_len`` and first token positions ``seq_off`` (host ints), and

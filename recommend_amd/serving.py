@@ -27,6 +27,9 @@ extend the S side at its end, so with no pruning before the last layer only the 
 Under ``seq_fusion='time'`` the S side is ordered by event time and has no [SEP]: new events of any present
 sequence land at its end as long as they are later than the request's cached latest event
 (``RequestCache.last_time``), so every behaviour can extend the cache.
+
+Cache precision (``OneTransServer(model, cache_dtype='bf16')``): the cached K/V rows stored rounded to
+bf16, one buffer per layer that ``extend_requests`` grows in place; the default 'fp32' keeps the f32 qkv rows.
 """
 
 from __future__ import annotations
@@ -47,13 +50,26 @@ def _cache_valid(valid, L_S: int, s: int):
     return None if valid is None else (valid, L_S - s, L_S)
 
 
+CACHE_DTYPES = ('fp32', 'bf16')
+
+
+def bf16_cache_nbytes(cfg, R: int, L_S: int, reserve: int = 0) -> int:
+    """Bytes of the K/V storage of a bf16 request cache: R · Σ_l cap_l · 2d · 2 with cap_l = Ic_l + reserve rows per
+    request in layer l (Ic_l: the layer's S rows, ``request_schedule``).  The fp32 cache keeps Ic_l · 3d · 4 a row."""
+    return R * sum(e['s'] + reserve for e in request_schedule(cfg, L_S)) * 2 * cfg.hidden_dim * 2
+
+
 class RequestCache:
-    """Stage-I output for R requests: per layer the S-side qkv rows [R*Ic, 3d] (k at col d, v at 2d)
-    and Ic, the number of S tokens in that layer's input."""
+    """Stage-I output for R requests, per layer Ic (the number of S tokens in that layer's input) and their K/V:
+    ``dtype`` 'fp32': 'kv', the S-side qkv rows [R*Ic, 3d] (k at col d, v at 2d);
+    ``dtype`` 'bf16': 'kv16', one bfloat16 buffer [R, cap, 2d] (k at col 0, v at col d) whose first Ic rows of every
+    request are this cache's; 'cap' its rows per request and 'high' a one-element list, shared by the caches that
+    share the buffer, of the rows filled in it (``extend_requests`` appends in place behind them)."""
 
     def __init__(self, R: int, L_S: int, layers: List[Dict], present=(), last_time: Optional[torch.Tensor] = None,
-                 valid: Optional[torch.Tensor] = None):
+                 valid: Optional[torch.Tensor] = None, dtype: str = 'fp32'):
         self.R, self.L_S, self.layers = R, L_S, layers
+        self.dtype = dtype
         # seq_padding_mask: the S tokens' validity, uint8 [R, L_S]; a layer with Ic cached rows reads its last Ic columns
         self.valid = valid
         self.present = tuple(present)          # sequence names present in the requests, config order
@@ -61,11 +77,25 @@ class RequestCache:
         # extend_requests appends only events after it
         self.last_time = last_time
 
+    def nbytes(self) -> int:
+        """Bytes of the K/V storage this cache holds (a bf16 buffer counts whole, reserve rows included)."""
+        ts = [lay.get('kv16' if self.dtype == 'bf16' else 'kv') for lay in self.layers]
+        return sum(t.numel() * t.element_size() for t in ts if t is not None)
+
 
 class OneTransServer:
-    """Cached two-stage inference on a ``OneTransModel`` (weights shared, nothing copied)."""
+    """Cached two-stage inference on a ``OneTransModel`` (weights shared, nothing copied).
 
-    def __init__(self, model):
+    ``cache_dtype`` 'bf16': the request cache keeps each layer's S-side K/V rounded to bf16 (round to nearest even),
+    a third of the fp32 cache's bytes (which also holds the Q columns).  Rounding happens only when a row is
+    stored: stage I's own self-attention runs on the un-rounded f32 rows, a candidate's own rows stay f32, and the
+    cached attention (ot_attn_fwd_cached_kv16) is exact in f32 over [rounded cache ; own rows] — the scores equal the
+    fp32 server's on a cache whose K/V columns were rounded, up to f32 summation order."""
+
+    def __init__(self, model, cache_dtype: str = 'fp32'):
+        if cache_dtype not in CACHE_DTYPES:
+            raise ValueError(f'OneTransServer: cache_dtype {cache_dtype!r}, expected one of {CACHE_DTYPES}')
+        self.cache_dtype = cache_dtype
         self.m = model
         cfg = model.config
         if getattr(cfg, 'pyramid_select', 'tail') != 'tail':
@@ -86,12 +116,16 @@ class OneTransServer:
     # ------------------------------------------------------------------ stage I
     @torch.no_grad()
     @K.in_model_precision
-    def encode_requests(self, seq_features: Dict[str, torch.Tensor]) -> RequestCache:
+    def encode_requests(self, seq_features: Dict[str, torch.Tensor], reserve: int = 0) -> RequestCache:
         """Tokenize the requests' sequences (model.py:256-277) and run the S side of every layer;
-        cache each layer's S-side K/V."""
+        cache each layer's S-side K/V.  ``reserve`` (cache_dtype 'bf16'): rows per request every layer's buffer
+        holds beyond its Ic, for ``extend_requests`` to append in place."""
         from .model import _Tokenize
         m = self.m
         cfg = m.config
+        reserve = int(reserve)
+        if reserve < 0:
+            raise ValueError(f'encode_requests: reserve={reserve} is negative')
         if not seq_features:
             raise ValueError('encode_requests: no sequence features')
         plan = m._plan({}, seq_features)
@@ -99,18 +133,41 @@ class OneTransServer:
         x = s_rows(_Tokenize.apply(m.flat, m, plan), plan)                # NS rows zero (no NS features)
         # seq_padding_mask: the S columns of the plan's validity array (its lengths come with seq_features)
         valid = plan['valid0'][:, :L_S].contiguous() if m.padding_mask else None
+        bf16 = self.cache_dtype == 'bf16'
         layers = []
         for l, e in enumerate(self.schedule(L_S)):
             s, kS = e['s'], e['kS']
             if s == 0:
-                layers.append({'Ic': 0, 'kv': None})
+                layers.append(self._kv16_layer(None, R, 0, reserve, 0) if bf16 else {'Ic': 0, 'kv': None})
                 continue
             x, qkv, _ = span_forward(m, l, x, R, s, kS, 0, e['I'], cached=False,     # S queries see S keys only
                                      valid=_cache_valid(valid, L_S, s))
-            layers.append({'Ic': s, 'kv': qkv})
+            # bf16: the rounded K | V rows are all that stays (qkv, with its Q columns, is dropped here)
+            layers.append(self._kv16_layer(qkv, R, s, s + reserve, 0) if bf16 else {'Ic': s, 'kv': qkv})
         present = [n for n in cfg.feature_config['sequence_features'] if n in seq_features]
         last_time = plan['last_time'].clone() if m.time_fusion else None
-        return RequestCache(R, L_S, layers, present, last_time, valid)
+        return RequestCache(R, L_S, layers, present, last_time, valid, self.cache_dtype)
+
+    def _kv16_layer(self, qkv, R: int, rows: int, cap: int, Ic: int, old: Optional[Dict] = None) -> Dict:
+        """A bf16 cache layer of ``Ic + rows`` rows: the K | V columns of ``qkv`` [R*rows, 3d] packed behind the Ic
+        rows of layer ``old`` — in its buffer when they fit and the buffer ends at those Ic rows (its high-water
+        mark), else in a new buffer of ``cap`` rows per request that takes one copy of them."""
+        d = self.m.config.hidden_dim
+        if old is not None and Ic + rows <= old['cap'] and old['high'][0] == Ic:
+            buf, cap, high = old['kv16'], old['cap'], old['high']
+        else:
+            buf, high = torch.empty(R, cap, 2 * d, dtype=torch.bfloat16, device=self.m.device), [Ic]
+            if Ic > 0:
+                buf[:, :Ic] = old['kv16'][:, :Ic]
+        if rows > 0:
+            K.kv_pack_bf16(qkv, 3 * d, R, rows, d, buf, 2 * d, cap, Ic)
+        high[0] = Ic + rows
+        return {'Ic': Ic + rows, 'kv16': buf, 'cap': cap, 'high': high}
+
+    def _check_cache(self, who: str, cache: RequestCache) -> None:
+        if cache.dtype != self.cache_dtype:
+            raise ValueError(f'{who}: a {cache.dtype!r} request cache was given to a server with cache_dtype '
+                             f'{self.cache_dtype!r}')
 
     # ------------------------------------------------------------------ cross-request append
     @torch.no_grad()
@@ -132,11 +189,18 @@ class OneTransServer:
         latest time (``cache.last_time``).  A time equal to it is accepted only for the last configured sequence
         (only there is the tie certain to sort last: the key is (time, sequence, position)).  Checked with one
         small read-back before anything is launched; a violation raises ValueError.  ``new_times`` is ignored
-        under 'sep'."""
+        under 'sep'.
+
+        cache_dtype 'bf16': the new rows go into the layer buffers in place — no copy, the returned cache shares the
+        buffers and ``cache`` stays valid — when they fit (``encode_requests(reserve=)``) and ``cache`` ends at the
+        buffer's high-water mark; otherwise each layer gets a buffer of max(Ic + dL, 2·cap) rows per request and one
+        copy (an old cache extended a second time forks this way)."""
         from .model import _Tokenize
         m = self.m
         cfg = m.config
         d = cfg.hidden_dim
+        self._check_cache('extend_requests', cache)
+        bf16 = self.cache_dtype == 'bf16'
         seqs = cfg.feature_config['sequence_features']
         if m.time_fusion:
             if seq_name not in seqs or seq_name not in cache.present:
@@ -174,6 +238,14 @@ class OneTransServer:
             Ic = e_old['s']
             lay = cache.layers[l]
             keep = e_new['kS'] - e_old['kS']                              # new S rows kept by this layer
+            if bf16:
+                # the new tokens attend over the bf16 rows and their own f32 rows; then their K/V are appended, in
+                # place when the buffer has room behind this cache's rows (the old cache reads only its first Ic)
+                x, qkv, _ = span_forward(m, l, x, R, dL, dL if keep == dL else 0, Ic, e_new['I'], cached=True,
+                                         kv16=(lay['kv16'], lay['cap']) if Ic > 0 else None, Ic=Ic, req=req, R=R,
+                                         valid=_cache_valid(cache.valid, cache.L_S, Ic))
+                layers.append(self._kv16_layer(qkv, R, dL, max(Ic + dL, 2 * lay['cap']), Ic, lay))
+                continue
             x, qkv, _ = span_forward(m, l, x, R, dL, dL if keep == dL else 0, Ic, e_new['I'], cached=True,
                                      kv=lay['kv'] if Ic > 0 else None, req=req, R=R,
                                      valid=_cache_valid(cache.valid, cache.L_S, Ic))
@@ -181,7 +253,7 @@ class OneTransServer:
             layers.append({'Ic': Ic + dL, 'kv': kv.reshape(R * (Ic + dL), 3 * d)})
         valid = (torch.cat([cache.valid, torch.ones(R, dL, dtype=torch.uint8, device=m.device)], 1)
                  if m.padding_mask else None)
-        return RequestCache(R, cache.L_S + dL, layers, cache.present, last_time, valid)
+        return RequestCache(R, cache.L_S + dL, layers, cache.present, last_time, valid, self.cache_dtype)
 
     def _check_new_times(self, cache: RequestCache, seq_name: str, new_events, new_times) -> torch.Tensor:
         """``extend_requests`` under seq_fusion='time': the new events' times as a device int64 [R, dL] tensor,
@@ -216,6 +288,8 @@ class OneTransServer:
         heads: (probs [T, C], req as device int32 [C])."""
         from .model import _Head, _Tokenize
         m = self.m
+        self._check_cache(who, cache)
+        bf16 = self.cache_dtype == 'bf16'
         plan = m._plan(non_seq_features, {})
         C = plan['B']
         if m.padding_mask and cache.valid is None:
@@ -228,6 +302,11 @@ class OneTransServer:
             lay = cache.layers[l]
             if lay['Ic'] != s:
                 raise OneTransHipError(f'{who}: request cache does not match the schedule')
+            if bf16:
+                x, _, _ = span_forward(m, l, x, C, n, kN, s, e['I'], cached=True,
+                                       kv16=(lay['kv16'], lay['cap']) if s > 0 else None, Ic=s, req=req, R=cache.R,
+                                       valid=_cache_valid(cache.valid, cache.L_S, s))
+                continue
             x, _, _ = span_forward(m, l, x, C, n, kN, s, e['I'], cached=True, kv=lay['kv'] if s > 0 else None,
                                    req=req, R=cache.R, valid=_cache_valid(cache.valid, cache.L_S, s))
         probs, _ = _Head.apply(m.flat, x, m)                               # [T, C]
@@ -295,9 +374,9 @@ class OneTransInferenceEngine:
     """The reference's inference engine surface (examples/inference_example.py:21-219): load a saved
     model directory (config.json + weights, train.py:281-291), preprocess, single / batch inference,
     latency statistics.  ``score_candidates`` adds the two-stage path: one user's sequences once,
-    many candidates against the cache."""
+    many candidates against the cache (``cache_dtype`` 'fp32' or 'bf16': ``OneTransServer``'s request cache)."""
 
-    def __init__(self, model_path: str, device=None):
+    def __init__(self, model_path: str, device=None, cache_dtype: str = 'fp32'):
         import json
         import os
         from .config import OneTransConfig
@@ -312,7 +391,7 @@ class OneTransInferenceEngine:
             raise FileNotFoundError(f'model weights not found: {w}')
         self.model = OneTransModel(self.config, device=device)
         self.model.load_weights(w)
-        self.server = OneTransServer(self.model)
+        self.server = OneTransServer(self.model, cache_dtype)      # 'bf16': score_candidates / rank_candidates
         self.reset_stats()
 
     # ------------------------------------------------------------------ inference_example.py:63-92

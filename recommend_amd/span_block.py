@@ -68,7 +68,7 @@ def check_req(who: str, req, R: int, C: int, ordered: bool) -> None:
 
 def span_forward(m, l: int, x: torch.Tensor, B: int, I: int, Kq: int, p0: int, I_full: int, *, cached: bool,
                  kv=None, req=None, R: int = 0, seed: int = 0, rate: float = 0.0, for_backward: bool = False,
-                 valid=None):
+                 valid=None, kv16=None, Ic: int = 0):
     """OneTransBlock.call (model.py:186-200) on B spans of I rows (positions p0.. of a layer of I_full tokens),
     keeping the last Kq; plain kernel forms.  Returns (x2 [B*Kq, d], qkv [B*I, 3d], saved); Kq = 0: only the K/V
     rows of qkv are produced and x2 is None.
@@ -80,7 +80,13 @@ def span_forward(m, l: int, x: torch.Tensor, B: int, I: int, Kq: int, p0: int, I
     backward's weight gradient reads every column), the cached attention writes its lse, and ``saved`` is what the
     backward reads (x, rstd1[, qkv, o, lse, x1, rstd2, u]).
     ``valid`` (seq_padding_mask): the key-padding mask as (uint8 tensor, element offset, row stride) — of the span's
-    own I keys when not ``cached``, of the Ic cached rows ([R, .]) when ``cached`` (the span's own rows are valid)."""
+    own I keys when not ``cached``, of the Ic cached rows ([R, .]) when ``cached`` (the span's own rows are valid).
+    ``kv16`` (serving with a bf16 request cache), instead of ``kv`` when ``cached``: (bfloat16 tensor [R, cap, ld16],
+    cap) — request r's ``Ic`` cached rows are the first Ic of its cap rows, K at col 0 and V at col d; ``Ic`` is given
+    (the buffer may hold reserve rows).  Inference only: it raises with ``for_backward``."""
+    if kv16 is not None and (for_backward or not cached or kv is not None):
+        raise ValueError('span_forward: kv16 (a bf16 request cache) is an alternative to kv for cached inference; '
+                         'the backward reads f32 K/V rows')
     cfg = m.config
     d, f, H = cfg.hidden_dim, cfg.ffn_dim, cfg.num_heads
     hd = d // H
@@ -107,7 +113,11 @@ def span_forward(m, l: int, x: torch.Tensor, B: int, I: int, Kq: int, p0: int, I
            mt['rows'][0], a_xform=OT_AX_RMSNORM, rstd=rstd1, gamma=g1, m_rows=mp['tail'].nrows)
     o = torch.empty(B * Kq, d, device=dev)
     lse = torch.empty(B * H * Kq, device=dev) if for_backward or not cached else None
-    if cached:
+    if cached and kv16 is not None:
+        buf, req_stride = kv16
+        K.attn_fwd_cached_kv16(qkv, 3 * d, buf, buf.shape[-1], req_stride, req, B, H, Ic, I, Kq, hd, o,
+                               valid if Ic > 0 else None, lse)
+    elif cached:
         Ic = kv.shape[0] // R if kv is not None else 0
         if valid is not None:
             K.attn_fwd_cached_masked(qkv, 3 * d, (kv, d) if kv is not None else None, 3 * d, req, B, H, Ic, I, Kq, hd,
