@@ -45,17 +45,20 @@ __global__ void piece_count_kernel(const int32_t* __restrict__ seg_start, const 
   pcount[s] = s < U ? (seg_start[s + 1] - seg_start[s] + PIECE - 1) / PIECE : 0;
 }
 
-// TPS threads per piece / segment, float4 each (E = 4*TPS*k)
+// tps = min(E / 4, 64) threads per piece / segment, one float4 each per pass of the column loop (any E % 4 == 0:
+// the last pass may be partial).  A 256-thread block holds 256 / tps whole groups; when tps does not divide 256 the
+// threads past the last whole group are idle: they must not run on into the next block's first piece / segment.
 __global__ __launch_bounds__(256) void piece_sum_kernel(const float* __restrict__ grads, int E,
                                                         const int32_t* __restrict__ perm,
                                                         const int32_t* __restrict__ seg_start,
                                                         const int32_t* __restrict__ pstart,
                                                         const int32_t* __restrict__ nuniq, int tps, float* psum) {
   const int ppb = 256 / tps;
-  const int64_t pc = (int64_t)blockIdx.x * ppb + threadIdx.x / tps;
+  const int lp = threadIdx.x / tps;
+  const int64_t pc = (int64_t)blockIdx.x * ppb + lp;
   const int lt = threadIdx.x % tps;
   const int U = nuniq[0];
-  if (pc >= pstart[U]) return;
+  if (lp >= ppb || pc >= pstart[U]) return;
   const int lo = last_start_le(pstart, U, pc);   // the piece's segment
   const int i0 = seg_start[lo] + (int)(pc - pstart[lo]) * PIECE;
   const int i1 = min(i0 + PIECE, seg_start[lo + 1]);
@@ -73,10 +76,11 @@ __global__ __launch_bounds__(256) void seg_sum_kernel(const float* __restrict__ 
                                                       const int32_t* __restrict__ nuniq, int tps, float* gsum,
                                                       float* sq_part) {
   const int spb = 256 / tps;
-  const int64_t s = (int64_t)blockIdx.x * spb + threadIdx.x / tps;
+  const int ls = threadIdx.x / tps;
+  const int64_t s = (int64_t)blockIdx.x * spb + ls;
   const int lt = threadIdx.x % tps;
   float sq = 0.f;
-  if (s < nuniq[0] && ksorted[seg_start[s]] != 0xFFFFFFFFu) {
+  if (ls < spb && s < nuniq[0] && ksorted[seg_start[s]] != 0xFFFFFFFFu) {
     const int b = pstart[s], e = pstart[s + 1];
     for (int c = lt * 4; c < E; c += tps * 4) {
       f32x4 acc = {0.f, 0.f, 0.f, 0.f};
@@ -108,9 +112,10 @@ __global__ __launch_bounds__(256) void adagrad_apply_kernel(float* table, float*
                                                             const float* __restrict__ scale, int tps, float lr,
                                                             float eps) {
   const int spb = 256 / tps;
-  const int64_t s = (int64_t)blockIdx.x * spb + threadIdx.x / tps;
+  const int ls = threadIdx.x / tps;
+  const int64_t s = (int64_t)blockIdx.x * spb + ls;
   const int lt = threadIdx.x % tps;
-  if (s >= nuniq[0]) return;
+  if (ls >= spb || s >= nuniq[0]) return;
   const uint32_t key = ksorted[seg_start[s]];
   if (key == 0xFFFFFFFFu) return;
   const float sc = scale[0];
@@ -136,9 +141,10 @@ __global__ __launch_bounds__(256) void scatter_rows_kernel(float* dense, int E, 
                                                            const int32_t* __restrict__ nuniq,
                                                            const float* __restrict__ gsum, int tps) {
   const int spb = 256 / tps;
-  const int64_t s = (int64_t)blockIdx.x * spb + threadIdx.x / tps;
+  const int ls = threadIdx.x / tps;
+  const int64_t s = (int64_t)blockIdx.x * spb + ls;
   const int lt = threadIdx.x % tps;
-  if (s >= nuniq[0]) return;
+  if (ls >= spb || s >= nuniq[0]) return;
   const uint32_t key = ksorted[seg_start[s]];
   if (key == 0xFFFFFFFFu) return;
   for (int c = lt * 4; c < E; c += tps * 4)

@@ -83,7 +83,7 @@ __global__ void hash_uniform_rows_kernel(float* out, int64_t local_rows, int E, 
   const uint32_t h1 = fmix32((uint32_t)(gid * (uint64_t)E + c) * 0x9E3779B1u + seed);
   const uint32_t h2 = fmix32(h1 ^ (uint32_t)(gid >> 32) ^ 0x85EBCA77u);
   const float u = (float)(h2 >> 8) * (1.f / 16777216.f);
-  out[t] = lo + (hi - lo) * u;
+  out[t] = fmaf(hi - lo, u, lo);   // one rounding, spelled out: the value is part of the table's definition
 }
 
 struct RouteWs {

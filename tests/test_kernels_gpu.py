@@ -378,7 +378,7 @@ def test_pyramid_select(dev, B, I, Kk, nforce, scored):
         np.testing.assert_array_equal(got, np.broadcast_to(np.arange(I - Kk, I), (B, Kk)))   # model.py:296
 
 
-@pytest.mark.parametrize('d', [64, 128, 256, 512])
+@pytest.mark.parametrize('d', [64, 128, 192, 256, 384, 512])
 def test_rmsnorm(dev, d):
     torch.manual_seed(1)
     rows, Kq, I = 600, 5, 12
