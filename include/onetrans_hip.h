@@ -447,6 +447,47 @@ int ot_attn_bwd_cached(const float* qkv, int64_t ld, const float* kv_cache, int6
                        const float* lse, float* dqkv, float* dkv_cache, int accumulate, void* workspace,
                        size_t ws_bytes, void* stream);
 
+/* ---- one-query attention folded through the shared K / V projection (attention_fold.hip) -----
+ * The last layer keeps one query per sample (K = 1, the last position, which sees every key).  For the keys of
+ * weight group 0 the projection K_j = Wk0^T (gamma o xh_j), xh_j = x_j rstd_j, need not be formed: head h's score is
+ * <xh_j, gamma o (Wk0[:, h] q_h)> / sqrt(hd) and its value sum Wv0[:, h]^T (gamma o y_h), y_h = sum_j p_h[j] xh_j.
+ * The keys at positions ded0 <= p < ded1 (the dedicated groups) keep their projected rows.
+ *   x [B*I, ldx], rstd [B*I], gamma [d]: the layer input, its RMSNorm rstd and norm1's weight
+ *   w [d][ldw >= 3d]: group 0's Wqkv (Wk at column d, Wv at 2d); wT [3d][ldwT >= d]: its transpose
+ *   qkv [B*I, ldqkv]: q in columns 0..d of each sample's last row, K | V in columns d..3d of the dedicated rows
+ *   o [B, d], lse [B, H] (natural log, ot_attn_fwd's layout at K = 1), y [B, H, d]
+ * ot_attn_fold_supported: d = 128 with 2 or 4 heads (anything else: OT_ERR_UNSUPPORTED; the caller runs ot_attn_fwd).
+ * ot_attn_fold_bwd, given dout [B, d] and the forward's o / lse / y, writes
+ *   dx [B*I, lddx]: for a group-0 row the gradient through its use as a key, norm1's backward applied; zero for a
+ *     dedicated row; the query row also gets dx1[b] (optional, [B, d]: the residual branch) added
+ *   dqkv [B*nf, lddqkv >= 3d], nf = ot_attn_fold_rows(I, ded0, ded1): row b*nf + (p - ded0) of dedicated position p
+ *     holds 0 | dK | dV; the query's row (that row when it is dedicated, else b*nf + ded1 - ded0) holds dq in columns
+ *     0..d (and 0 in d..3d when it is not dedicated)
+ *   z [B, H, d]: z_h = sum_j ds_h[j] xh_j;  dgpart [B, d]: each sample's part of norm1's dgamma
+ * ot_attn_fold_dw: dW[k][d + n] (+)= gamma[k] sum_b z[b][head(n)][k] q[b][n] and dW[k][2d + n] (+)= gamma[k] sum_b
+ * y[b][head(n)][k] dout[b][n] (dW: group 0's Wqkv gradient [d][lddw >= 3d]); ot_attn_fold_dgamma: dgamma (+)= sum_b
+ * dgpart[b].  Both sum per-chunk partials in a fixed order (no float atomics); workspace: ot_attn_fold_workspace_size.
+ * ot_last_fold: whether the model's last block takes this path where its gate holds (1, default; environment
+ * variable ONETRANS_LAST_FOLD) or the ot_attn_fwd launches (0).  Process-wide; on = -1 only queries; returns the
+ * previous setting.  The library only keeps the setting: the host layer reads it. */
+int ot_attn_fold_supported(int d, int H);
+int ot_attn_fold_rows(int I, int ded0, int ded1);
+int ot_attn_fold_fwd(const float* x, int64_t ldx, const float* rstd, const float* gamma, const float* w, int64_t ldw,
+                     const float* wT, int64_t ldwT, const float* qkv, int64_t ldqkv, int B, int H, int I,
+                     int head_dim, int ded0, int ded1, float* o, float* lse, float* y, void* stream);
+int ot_attn_fold_bwd(const float* x, int64_t ldx, const float* rstd, const float* gamma, const float* w, int64_t ldw,
+                     const float* wT, int64_t ldwT, const float* qkv, int64_t ldqkv, int B, int H, int I,
+                     int head_dim, int ded0, int ded1, const float* o, const float* dout, const float* lse,
+                     const float* y, const float* dx1, float* dx, int64_t lddx, float* dqkv, int64_t lddqkv, float* z,
+                     float* dgpart, void* stream);
+size_t ot_attn_fold_workspace_size(int B, int d);
+int ot_attn_fold_dw(const float* z, const float* y, const float* qkv, int64_t ldqkv, const float* dout,
+                    const float* gamma, int B, int H, int I, int head_dim, float* dW, int64_t lddw, int accumulate,
+                    void* workspace, size_t ws_bytes, void* stream);
+int ot_attn_fold_dgamma(const float* dgpart, int B, int d, float* dgamma, int accumulate, void* workspace,
+                        size_t ws_bytes, void* stream);
+int ot_last_fold(int on);
+
 /* ---- padding mask (attention.hip, seqfuse.hip) ---------------------------------------------
  * Variable-length histories: behaviour sequences arrive left-padded to their cap, and with a key-padding mask a
  * padding event is no key for any other token.  key_valid is a byte per (sample, key): key_valid[b * ldv + j] != 0

@@ -210,6 +210,16 @@ SIGNATURES = {
     'ot_kv_pack_bf16': (c_int, [P, I64, c_int, I64, c_int, P, I64, I64, I64, P]),
     'ot_attn_fwd_cached_kv16': (c_int, [P, I64, P, I64, I64, P, c_int, c_int, c_int, c_int, c_int, c_int, P, I64, P, P,
                                         P]),
+    'ot_attn_fold_supported': (c_int, [c_int, c_int]),
+    'ot_attn_fold_rows': (c_int, [c_int, c_int, c_int]),
+    'ot_attn_fold_fwd': (c_int, [P, I64, P, P, P, I64, P, I64, P, I64, c_int, c_int, c_int, c_int, c_int, c_int, P, P,
+                                 P, P]),
+    'ot_attn_fold_bwd': (c_int, [P, I64, P, P, P, I64, P, I64, P, I64, c_int, c_int, c_int, c_int, c_int, c_int, P, P,
+                                 P, P, P, P, I64, P, I64, P, P, P]),
+    'ot_attn_fold_workspace_size': (c_size_t, [c_int, c_int]),
+    'ot_attn_fold_dw': (c_int, [P, P, P, I64, P, P, c_int, c_int, c_int, c_int, P, I64, c_int, P, c_size_t, P]),
+    'ot_attn_fold_dgamma': (c_int, [P, c_int, c_int, P, c_int, P, c_size_t, P]),
+    'ot_last_fold': (c_int, [c_int]),
     'ot_ns_bag_pool': (c_int, [P, c_int, c_int, P, I64, P, P]),
     'ot_ns_bag_grad_pack': (c_int, [P, c_int, c_int, P, I64, P, P, P, P]),
 }

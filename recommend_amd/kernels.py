@@ -478,6 +478,71 @@ def attn_bwd(qkv, ld, out, dout, lse, B, H, I, K, hd, dqkv, qpos=None, dq_part_b
         _probe.end('attention', 8.0 * (K * I - K * (K - 1) / 2) * hd * H * B, ev, f'bwd I{I} K{K} hd{hd}')
 
 
+def last_fold(on: int = -1) -> int:
+    """ot_last_fold: whether the last block (one query per sample) takes the folded attention where its gate holds
+    (model._fold_gate) — 1 (default; ONETRANS_LAST_FOLD) or 0: the K/V projection of every row and ot_attn_fwd — or
+    query (-1); returns the previous setting."""
+    return _lib.size('ot_last_fold', int(on))
+
+
+def attn_fold_supported(d: int, H: int) -> bool:
+    return bool(_lib.size('ot_attn_fold_supported', int(d), int(H)))
+
+
+def attn_fold_rows(I: int, ded0: int, ded1: int) -> int:
+    """Rows per sample of the fold backward's compact dqkv: the dedicated positions [ded0, ded1) plus the query."""
+    return _lib.size('ot_attn_fold_rows', int(I), int(ded0), int(ded1))
+
+
+def _fold_common(x, ldx, rstd, gamma, w, ldw, wT, ldwT, qkv, ldqkv, B, H, I, hd, ded):
+    return (ptr(x), ldx, ptr(rstd), ptr(gamma), ptr(w), ldw, ptr(wT), ldwT, ptr(qkv), ldqkv, B, H, I, hd, ded[0],
+            ded[1])
+
+
+def attn_fold_fwd(x, ldx, rstd, gamma, w, ldw, wT, ldwT, qkv, ldqkv, B, H, I, hd, ded, o, lse, y) -> None:
+    """ot_attn_fold_fwd: the one-query attention of the last layer on the raw rows of the shared-weight keys;
+    ``ded`` = (first, end) of the dedicated key positions.  Writes o [B, d], lse [B, H], y [B, H, d]."""
+    ev = _probe.begin() if _probe is not None else None
+    call('ot_attn_fold_fwd', *_fold_common(x, ldx, rstd, gamma, w, ldw, wT, ldwT, qkv, ldqkv, B, H, I, hd, ded),
+         ptr(o), ptr(lse), ptr(y), stream())
+    if ev is not None:
+        d = H * hd
+        _probe.end('attention', 4.0 * I * d * H * B, ev, f'fold_fwd I{I} hd{hd}', 4.0 * B * I * (d + 1))
+
+
+def attn_fold_bwd(x, ldx, rstd, gamma, w, ldw, wT, ldwT, qkv, ldqkv, B, H, I, hd, ded, o, dout, lse, y, dx1, dx, lddx,
+                  dqkv, lddqkv, z, dgpart) -> None:
+    """ot_attn_fold_bwd: dx of every row of the layer input (through its use as a key; zero for a dedicated row,
+    + dx1 on the query row), the compact dqkv rows of the dedicated keys and the query, z and the dgamma parts."""
+    ev = _probe.begin() if _probe is not None else None
+    call('ot_attn_fold_bwd', *_fold_common(x, ldx, rstd, gamma, w, ldw, wT, ldwT, qkv, ldqkv, B, H, I, hd, ded),
+         ptr(o), ptr(dout), ptr(lse), ptr(y), ptr(dx1), ptr(dx), lddx, ptr(dqkv), lddqkv, ptr(z), ptr(dgpart),
+         stream())
+    if ev is not None:
+        d = H * hd
+        _probe.end('attention', 10.0 * I * d * H * B, ev, f'fold_bwd I{I} hd{hd}', 8.0 * B * I * (d + 1))
+
+
+def attn_fold_dw(z, y, qkv, ldqkv, dout, gamma, B, H, I, hd, dW, lddw, accumulate: bool = False) -> None:
+    """ot_attn_fold_dw: group 0's dWk / dWv blocks from z / y and q / dout (fixed-order partial sums)."""
+    ws = workspace(size('ot_attn_fold_workspace_size', B, H * hd), z.device)
+    ev = _probe.begin() if _probe is not None else None
+    call('ot_attn_fold_dw', ptr(z), ptr(y), ptr(qkv), ldqkv, ptr(dout), ptr(gamma), B, H, I, hd, ptr(dW), lddw,
+         int(accumulate), ptr(ws), ws.numel(), stream())
+    if ev is not None:
+        d = H * hd
+        _probe.end('attention', 4.0 * B * d * d, ev, f'fold_dw B{B}', 8.0 * B * d * (H + 1))
+
+
+def attn_fold_dgamma(dgpart, B, d, dgamma, accumulate: bool = False) -> None:
+    """ot_attn_fold_dgamma: dgamma (+)= the samples' parts, summed in a fixed order."""
+    ws = workspace(size('ot_attn_fold_workspace_size', B, d), dgpart.device)
+    ev = _probe.begin() if _probe is not None else None
+    call('ot_attn_fold_dgamma', ptr(dgpart), B, d, ptr(dgamma), int(accumulate), ptr(ws), ws.numel(), stream())
+    if ev is not None:
+        _probe.end('attention', 0.0, ev, f'fold_dgamma B{B}', 4.0 * B * d)
+
+
 def _valid_arg(valid):
     """A key-padding mask argument (uint8 tensor, element offset, row stride) as (pointer, stride)."""
     t, off, ldv = valid

@@ -271,7 +271,31 @@ def layer_maps(cfg: OneTransConfig, B: int, I: int, K: int, p0: int = 0,
         tpos = pos[pos >= I - K]
         tail_pg.append([rows_for(tpos, lambda bb, pp: bb * I + pp),
                         rows_for(tpos, lambda bb, pp: bb * K + (pp - (I - K)))])
-    return {'all': build_map(all_pg), 'tail': build_map(tail_pg)}
+    maps = {'all': build_map(all_pg), 'tail': build_map(tail_pg)}
+    if K == 1 and p0 == 0 and I_full == I:
+        maps['fold'] = build_map(fold_rows(grp, B, I, G))
+    return maps
+
+
+def fold_positions(grp: np.ndarray, I: int) -> np.ndarray:
+    """Positions of the ``fold`` map: the dedicated-group keys and the one query (the last position), ascending."""
+    return np.union1d(np.nonzero(grp != 0)[0], [I - 1])
+
+
+def fold_rows(grp: np.ndarray, B: int, I: int, G: int):
+    """Per-group rows of the ``fold`` map (a layer keeping one query whose shared-weight keys are not projected: the
+    folded attention): space 0 = token rows b*I + p, space 1 = the compact rows b*nf + i of the
+    attention backward's dqkv, p = the i-th of the nf fold positions."""
+    fpos = fold_positions(grp, I)
+    nf = len(fpos)
+    b = np.arange(B)
+    per_group = []
+    for g in range(G):
+        idx = np.nonzero(grp[fpos] == g)[0]
+        tok = (b[:, None] * I + fpos[idx][None, :]).reshape(-1)
+        cmp_ = (b[:, None] * nf + idx[None, :]).reshape(-1)
+        per_group.append([tok, cmp_])
+    return per_group
 
 
 def head_map(B: int, T: int) -> RowMap:

@@ -221,8 +221,9 @@ def _block_forward(m, l, x, I, Kq, seed, training, rstd_in=None, select=False, n
     ``need_u=False`` (no backward will read this call's u): the fused FFN forward does not write it (saved u None).
     ``bounds``: this forward's PairBounds or None.
     ``kvalid``: layer 0's key-padding mask [B, L0] (uint8; seq_padding_mask) or None; the layer reads its last I columns.
-    Returns (x2, rstd_out, saved, pos, inv, rate); saved = (x, rstd1, qkv, o, lse, x1, rstd2, u, h, xn1, x1n);
-    h = the stored bf16 gelu(u), xn1 / x1n = the bf16 normalised QKV / FFN1 inputs (bf16 mode) or None."""
+    Returns (x2, rstd_out, saved, pos, inv, rate); saved = (x, rstd1, qkv, o, lse, x1, rstd2, u, h, xn1, x1n, yf);
+    h = the stored bf16 gelu(u), xn1 / x1n = the bf16 normalised QKV / FFN1 inputs (bf16 mode) or None, yf = the folded
+    attention's probability-weighted raw rows [B, H, d] (``fold_gate``) or None."""
     cfg = m.config
     d, f, H = cfg.hidden_dim, cfg.ffn_dim, cfg.num_heads
     hd = d // H
@@ -271,6 +272,9 @@ def _block_forward(m, l, x, I, Kq, seed, training, rstd_in=None, select=False, n
              and m.bimg(f'blk.{l}.wqkv') is not None)
     xn1 = torch.empty(B * I, d, dtype=torch.int16, device=dev) if xn_on else None
     x1n = torch.empty(B * Kq, d, dtype=torch.int16, device=dev) if xn_on else None
+    # the last layer's one query, folded through the shared K / V projection (ot_attn_fold_*)
+    fold = m.fold_gate(I, Kq, select, kvalid)
+    yf = None
     if xn1 is not None:
         full = Kq == I
         K.gemm_rms(OT_GEMM_NT, xa, d, d, ma['rows'][0], wqkv if full else (wqkv, d * d), 3 * d * d, d,
@@ -287,8 +291,11 @@ def _block_forward(m, l, x, I, Kq, seed, training, rstd_in=None, select=False, n
                3 * d, ma['rows'][0], a_xform=ax1, rstd=rstd1, gamma=g1, m_rows=maps['all'].nrows,
                bimg=m.bimg(f'blk.{l}.wqkv'))
     else:
-        K.gemm(OT_GEMM_NT, xa, d, d, ma['rows'][0], (wqkv, d * d), 3 * d * d, d, 2 * d, ma['tile_group'], na,
-               (qkv, d), 3 * d, ma['rows'][0], a_xform=ax1, rstd=rstd1, gamma=g1, m_rows=maps['all'].nrows,
+        # one query and shared-weight keys (fold): K / V of the dedicated rows only (and the query row, which the
+        # map holds for the backward) — the attention reads the other keys' raw rows
+        mkv, kvm = (maps['fold'].to(dev), maps['fold']) if fold is not None else (ma, maps['all'])
+        K.gemm(OT_GEMM_NT, xa, d, d, mkv['rows'][0], (wqkv, d * d), 3 * d * d, d, 2 * d, mkv['tile_group'],
+               kvm.ntiles, (qkv, d), 3 * d, mkv['rows'][0], a_xform=ax1, rstd=rstd1, gamma=g1, m_rows=kvm.nrows,
                bimg=m.bimg(f'blk.{l}.wqkv', tn0=d // TILE) if d % TILE == 0 else None)
         K.gemm(OT_GEMM_NT, xa, d, d, qrows, wqkv, 3 * d * d, d, d, mt['tile_group'], nt, qkv,
                3 * d, qrows, a_xform=ax1, rstd=rstd1, gamma=g1, m_rows=maps['tail'].nrows,
@@ -311,9 +318,14 @@ def _block_forward(m, l, x, I, Kq, seed, training, rstd_in=None, select=False, n
     pwo_f = m.gemm_pair(f'blk.{l}.wo', 'fwd')
     # (the masked attention reports no bounds: O's row maxima then come from a_row_bounds' own pass, and the Wo weight
     # gradient, without |O|, runs the exact split)
-    o_rep = kvalid is None and not m.attn_fp8 and K.attn_amax_supported(I, Kq, hd, qp_f)
+    # (nor does the folded attention: its B rows go through the row-absmax pass and the exact-split Wo gradient)
+    o_rep = kvalid is None and not m.attn_fp8 and fold is None and K.attn_amax_supported(I, Kq, hd, qp_f)
     rm_o = torch.empty(B * Kq, H, device=dev) if pwo_f and o_rep else None
-    if kvalid is not None:
+    if fold is not None:
+        yf = torch.empty(B * H, d, device=dev)
+        K.attn_fold_fwd(x, d, rstd1, g1, m.p(f'blk.{l}.wqkv'), 3 * d, wqkv, d, qkv, 3 * d, B, H, I, hd, fold, o, lse,
+                        yf)
+    elif kvalid is not None:
         K.attn_fwd_masked(qkv, 3 * d, B, H, I, Kq, hd, o, lse, _layer_valid(kvalid, I), qpos=qp_f)
     else:
         K.attn_fwd(qkv, 3 * d, B, H, I, Kq, hd, o, lse, qpos=qp_f, fp8=m.attn_fp8, dequant=m.attn_fp8 and training,
@@ -370,7 +382,7 @@ def _block_forward(m, l, x, I, Kq, seed, training, rstd_in=None, select=False, n
                         m.layout.images[(f'blk.{l}.w2', 'fwd')][1], b1, f, b2, d, f, x2, d, u_out=u, ldu=f,
                         u_amax=out('u'), rstd_out=rstd_out, eps=RMS_EPS, seed=seed, site=2 * l + 1, drop=rate,
                         tail=tail, m_rows=maps['tail'].nrows)
-        saved = (x, rstd1, qkv, o, lse, x1, rstd2, u, None, xn1, None)
+        saved = (x, rstd1, qkv, o, lse, x1, rstd2, u, None, xn1, None, yf)
         return x2, rstd_out, saved, pos, inv, rate
     umax = torch.empty(B * Kq, f // TILE, device=dev) if pair_w2 else None
     if h is not None:
@@ -394,7 +406,7 @@ def _block_forward(m, l, x, I, Kq, seed, training, rstd_in=None, select=False, n
                bimg=m.bimg(f'blk.{l}.w1'))
     if x1n is not None and h is None:                # the FFN1 GEMM above did not store it
         x1n = None
-    saved = (x, rstd1, qkv, o, lse, x1, rstd2, u, h, xn1, x1n)
+    saved = (x, rstd1, qkv, o, lse, x1, rstd2, u, h, xn1, x1n, yf)
     if not need_out:
         return None, None, saved, pos, inv, rate
     # x2 = x1 + drop(gelu(u) @ W2[g] + b2[g])     (model.py:154-161, 198)
@@ -468,9 +480,9 @@ class _Block(torch.autograd.Function):
             training, select = ctx.fwd_args
             _, _, saved, pos, inv, _ = _block_forward(m, l, xin, I, Kq, seed, training, rstd_in, select,
                                                       need_out=False, bounds=bounds, kvalid=kvalid)
-            x, rstd1, qkv, o, lse, x1, rstd2, u, h, xn1, x1n = saved
+            x, rstd1, qkv, o, lse, x1, rstd2, u, h, xn1, x1n, yf = saved
         else:
-            x, rstd1, qkv, o, lse, x1, rstd2, u, h, xn1, x1n = ctx.saved_tensors
+            x, rstd1, qkv, o, lse, x1, rstd2, u, h, xn1, x1n, yf = ctx.saved_tensors
         tail = (Kq, I, pos)
         cfg = m.config
         d, f, H = cfg.hidden_dim, cfg.ffn_dim, cfg.num_heads
@@ -586,6 +598,12 @@ class _Block(torch.autograd.Function):
         K.gemm_rms(OT_GEMM_NT, dyo, d, d, mt['rows'][1], m.p(f'blk.{l}.wo'), 0, d, d, mt['tile_group'], nt, do, d,
                    mt['rows'][1], epi=0, m_rows=maps['tail'].nrows, device=dev, bimg=m.bimg(f'blk.{l}.wo', 'dgrad'),
                    **a_row_bounds(pwo, dyo, d, B * Kq, d, rm_dyo))   # (a row-wise norm backward reports no maxima)
+        if yf is not None:     # the forward took the folded one-query attention
+            dx = _fold_backward(m, l, x, rstd1, qkv, o, lse, yf, do, dx1, B, I, maps['fold'], acc, dev)
+            m.side_block_done()
+            if m.grad_ready is not None:
+                m.grad_ready(l)
+            return None, dx, None, None, None, None, None, None, None, None, None, None
         # attention
         # bf16 mode, key-grouped backward (C5): dQKV in bf16 (OT_ATTN_DQKV_BF16) — the QKV dgrad (bf16 A) and
         # the Wqkv weight gradient (OT_WG_D_BF16) round it to bf16 anyway: the same values, half the bytes
@@ -636,6 +654,40 @@ class _Block(torch.autograd.Function):
         if m.grad_ready is not None:
             m.grad_ready(l)                     # this block's banks are final: the DP exchange may start
         return None, dx, None, None, None, None, None, None, None, None, None, None
+
+
+def _fold_backward(m, l, x, rstd1, qkv, o, lse, yf, do, dx1, B, I, fmap, acc, dev):
+    """Backward of the folded one-query attention and of the QKV projection around it (``fold_gate``): the fold
+    kernel streams x once and writes dx of every row (norm1's backward applied; + dx1 on the query row); dQKV exists
+    only for the ``fold`` map's rows (the dedicated keys and the query), compact, and the QKV dgrad adds their part
+    onto the dx rows in place; the Wqkv weight gradient runs over those rows, and group 0's dWk / dWv — the keys that
+    were never projected — come from z / y (ot_attn_fold_dw).  No PairBounds slots: these few-thousand-row weight
+    gradients run the exact split.  Returns dx [B*I, d]."""
+    cfg = m.config
+    d, H, G = cfg.hidden_dim, cfg.num_heads, cfg.num_groups
+    hd = d // H
+    ded = m.fold_ded(I)
+    mf = fmap.to(dev)
+    nf = K.attn_fold_rows(I, *ded)
+    g1, w = m.p(f'blk.{l}.norm1'), m.p(f'blk.{l}.wqkv')
+    dqkv = torch.empty(B * nf, 3 * d, device=dev)
+    dx = torch.empty(B * I, d, device=dev)
+    zf = torch.empty(B * H, d, device=dev)
+    dgp = torch.empty(B, d, device=dev)
+    K.attn_fold_bwd(x, d, rstd1, g1, w, 3 * d, m.pT(f'blk.{l}.wqkv'), d, qkv, 3 * d, B, H, I, hd, ded, o, do, lse, yf,
+                    dx1, dx, d, dqkv, 3 * d, zf, dgp)
+    pa_q = a_row_bounds(m.dgrad_pair(f'blk.{l}.wqkv'), dqkv, 3 * d, B * nf, 3 * d)
+    K.gemm_rms(OT_GEMM_NT, dqkv, 3 * d, 3 * d, mf['rows'][1], w, 3 * d * d, 3 * d, d, mf['tile_group'], fmap.ntiles,
+               dx, d, mf['rows'][0], epi=OT_EPI_RMSNORM_BWD, m_rows=fmap.nrows, nx=x, ldnx=d, ngamma=g1, nrstd=rstd1,
+               dres=dx, lddres=d, dgamma=m.g(f'blk.{l}.norm1'), accumulate_dgamma=acc, device=dev,
+               bimg=m.bimg(f'blk.{l}.wqkv', 'dgrad'), **pa_q)
+    K.attn_fold_dgamma(dgp, B, d, m.g(f'blk.{l}.norm1'), accumulate=True)
+    with m.side(x, dqkv, rstd1, zf, yf, qkv, do):
+        K.wgrad(x, d, mf['rows'][0], dqkv, 3 * d, mf['rows'][1], d, 3 * d, mf, fmap.chunks.shape[0], G,
+                m.g(f'blk.{l}.wqkv'), 3 * d * d, None, 0, a_xform=OT_AX_RMSNORM, rstd=rstd1, gamma=g1, accumulate=acc,
+                device=dev, m_rows=fmap.nrows, rowmap=fmap)
+        K.attn_fold_dw(zf, yf, qkv, 3 * d, do, g1, B, H, I, hd, m.g(f'blk.{l}.wqkv'), 3 * d, accumulate=True)
+    return dx
 
 
 def _wgrad_single(m, A, D, K_, N, mt, dW, acc, dev, mrows=0, rowmap=None, a_bound=None, d_bound=None):
@@ -1100,6 +1152,27 @@ class OneTransModel(nn.Module):
         if key not in self._maps:
             self._maps[key] = layer_maps(self.config, B, I, Kq, p0=p0, I_full=I_full)
         return self._maps[key]
+
+    def fold_ded(self, I: int):
+        """(first, end) of the dedicated-group key positions of a layer of I tokens, or None when they are not one
+        contiguous run (the folded attention, ot_attn_fold_*, takes them as a range)."""
+        key = ('fold', I)
+        if key not in self._aux_maps:
+            ded = [p for p in range(I) if self.config.group_of_position(p, I) != 0]
+            run = (ded[0], ded[-1] + 1) if ded else (0, 0)
+            self._aux_maps[key] = run if ded == list(range(*run)) else None
+        return self._aux_maps[key]
+
+    def fold_gate(self, I: int, Kq: int, select: bool, kvalid):
+        """Does a block of I tokens keeping Kq take the folded one-query attention?  Its dedicated
+        range (``fold_ded``) when it does, else None: the block then runs the K/V projection of every row and the
+        attention kernels, exactly as without the switch (ONETRANS_LAST_FOLD / K.last_fold)."""
+        cfg = self.config
+        if (Kq != 1 or I < 2 or select or kvalid is not None or self.attn_fp8 or not self.fuse_bwd
+                or K.matmul_mode() not in ('split', 'f32') or not K.last_fold()
+                or not K.attn_fold_supported(cfg.hidden_dim, cfg.num_heads)):
+            return None
+        return self.fold_ded(I)
 
     def head_rows(self, B):
         key = ('head', B)
