@@ -324,6 +324,45 @@ int ot_ffn_fused_fwd(const ot_ffn_fused_args* args, void* stream);
  * setting: the host layer reads it. */
 int ot_ffn_fused(int on);
 
+/* The fused FFN backward of the split mode at hidden width 128: the two input gradients of the FFN branch
+ *   dU = (dy2 @ W2[g]^T) * gelu'(u),  dx1 = norm2_bwd(dU @ W1[g]^T; x1, rstd, gamma) + dres  [, dx_masked = drop(dx1)]
+ * in one launch: a row tile's dU is written once (the W1 weight gradient and db1 read it) and multiplied from the
+ * accumulators, so it is not read back and its row maxima never pass through memory.  dU and *du_amax equal the FFN2
+ * dgrad launch's (ot_mixed_gemm_rms_img, OT_EPI_GELU_BWD, a_rowmax = dy2_rowmax) bit for bit; dx1 / dx_masked / dgamma
+ * differ from the FFN1 dgrad launch's (OT_EPI_RMSNORM_BWD [| OT_EPI_DROPOUT]) by rounding (a row scale per 128 columns
+ * of dU — the largest |dU| of the row's columns so far — instead of one per row, another k order).  The norm backward,
+ * dropout mask, dgamma, amax_out and rowabs_out arithmetic are that epilogue's. */
+typedef struct ot_ffn_fused_bwd_args {
+  size_t struct_size;                                  /* sizeof(ot_ffn_fused_bwd_args): any other value is refused */
+  const float* dy2; int64_t lddy2;                     /* gradient of the FFN branch's output, 128 floats per row */
+  const float* dy2_rowmax; int dy2_rowmax_n;           /* [dy2 row][n] parts of max |dy2| per row (a_rowmax) */
+  const int32_t* rows;                                 /* [ntiles * 128] row of dy2 / u / du / x1 / dx1 per tile row,
+                                                          -1 = none; NULL = identity */
+  const int32_t* tile_group; int ntiles;               /* weight group per tile (NULL: group 0) */
+  const uint16_t* w2_image; int w2_groups;             /* ot_split_images pair images of the dgrads: W2 (f / 128 column */
+  const uint16_t* w1_image; int w1_groups;             /* tiles of 8 units per group), W1 (f / 16 units per group) */
+  int f;                                               /* FFN width: a multiple of 128, at most 1024 */
+  const float* u; int64_t ldu;                         /* the forward's pre-activation */
+  float* du; int64_t lddu;
+  float* du_amax;                                      /* optional: *du_amax = max(*du_amax, max |du|) as amax_out */
+  const float* x1; int64_t ldx1;                       /* norm2's input, gamma and rstd */
+  const float* gamma; const float* rstd;
+  const float* dres; int64_t lddres;                   /* optional: added to dx1 (the residual branch's gradient) */
+  float* dx1; int64_t lddx1;
+  float* dx_masked; int64_t lddxm;                     /* with drop_rate > 0: drop(dx1) at (seed, site) */
+  float* dgamma; int accumulate_dgamma;
+  void* workspace; size_t ws_bytes;                    /* ot_mixed_gemm_rms_workspace_size(ntiles, 128) */
+  float* amax_out; float* rowabs_out; int rowabs_n;    /* optional, as ot_rms_epilogue's (of dx_masked, else dx1); rowabs_n 1 */
+  uint32_t seed, site; float drop_rate;                /* dropout as ot_mixed_gemm's (0: none) */
+  int tail_K, tail_I; const int32_t* tail_pos;
+} ot_ffn_fused_bwd_args;
+int ot_ffn_fused_bwd(const ot_ffn_fused_bwd_args* args, void* stream);
+/* Whether the model's block backward takes ot_ffn_fused_bwd where its form applies (1, default) or the FFN2 and FFN1
+ * dgrad launches (0); the environment variable ONETRANS_FFN_FUSED_BWD (0 / 1) sets the process's initial value.
+ * Process-wide; on = -1 only queries; returns the previous setting.  The library only keeps the setting: the host
+ * layer reads it. */
+int ot_ffn_fused_bwd_on(int on);
+
 /* ---- causal attention with a query tail (attention.hip) ----------------------------------
  * Replaces model.py:100-114 (einsum QK^T/sqrt(hd), band_part mask with -1e9, softmax, einsum PV)
  * and the pyramid gather of queries model.py:356/371 (only the last K of I queries computed).

@@ -63,6 +63,22 @@ class FfnFusedArgs(ctypes.Structure):
                 ('tail_K', c_int), ('tail_I', c_int), ('tail_pos', c_void_p)]
 
 
+class FfnFusedBwdArgs(ctypes.Structure):
+    """``ot_ffn_fused_bwd_args`` (include/onetrans_hip.h)."""
+    _fields_ = [('struct_size', c_size_t), ('dy2', c_void_p), ('lddy2', c_int64),
+                ('dy2_rowmax', c_void_p), ('dy2_rowmax_n', c_int), ('rows', c_void_p),
+                ('tile_group', c_void_p), ('ntiles', c_int),
+                ('w2_image', c_void_p), ('w2_groups', c_int), ('w1_image', c_void_p), ('w1_groups', c_int),
+                ('f', c_int), ('u', c_void_p), ('ldu', c_int64), ('du', c_void_p), ('lddu', c_int64),
+                ('du_amax', c_void_p), ('x1', c_void_p), ('ldx1', c_int64), ('gamma', c_void_p), ('rstd', c_void_p),
+                ('dres', c_void_p), ('lddres', c_int64), ('dx1', c_void_p), ('lddx1', c_int64),
+                ('dx_masked', c_void_p), ('lddxm', c_int64), ('dgamma', c_void_p), ('accumulate_dgamma', c_int),
+                ('workspace', c_void_p), ('ws_bytes', c_size_t),
+                ('amax_out', c_void_p), ('rowabs_out', c_void_p), ('rowabs_n', c_int),
+                ('seed', c_uint32), ('site', c_uint32), ('drop_rate', c_float),
+                ('tail_K', c_int), ('tail_I', c_int), ('tail_pos', c_void_p)]
+
+
 class SeqTime(ctypes.Structure):
     """``ot_seq_time`` (include/onetrans_hip.h): one sequence's times and its segment of the row map."""
     _fields_ = [('times', c_void_p), ('stride_b', c_int64), ('L', ctypes.c_int32), ('map_off', ctypes.c_int32)]
@@ -119,6 +135,8 @@ SIGNATURES = {
     'ot_plane_panel_launches': (c_int, []),
     'ot_ffn_fused_fwd': (c_int, [P, P]),
     'ot_ffn_fused': (c_int, [c_int]),
+    'ot_ffn_fused_bwd': (c_int, [P, P]),
+    'ot_ffn_fused_bwd_on': (c_int, [c_int]),
     'ot_split_images': (c_int, [P, P, c_int, I64, P, c_int, P]),
     'ot_attn_fwd': (c_int, [P, I64, c_int, c_int, c_int, c_int, P, c_int, P, P, c_int, P]),
     'ot_attn_fwd_fp8_workspace_size': (c_size_t, [c_int, c_int, c_int, c_int]),

@@ -405,6 +405,43 @@ def ffn_fused_fwd(x1: Ptrish, ldx1: int, rows: Ptrish, tile_group: Ptrish, ntile
                    + 4.0 * M * (1 + (rstd_out is not None)), 3)
 
 
+def ffn_fused_bwd_on(on: int = -1) -> int:
+    """ot_ffn_fused_bwd_on: whether the block backward takes the fused FFN backward kernel where its form applies
+    (split mode, hidden width 128, pair-form W2 / W1 dgrad images, float32 dU, ffn width a multiple of 128 up to
+    ``FFN_FUSED_MAX_F``, the norm2 backward fused) — 1 (default), or 0: the FFN2 and FFN1 dgrad launches — or query
+    (-1); returns the previous setting.  ``ONETRANS_FFN_FUSED_BWD`` sets the process's initial value."""
+    return _lib.size('ot_ffn_fused_bwd_on', int(on))
+
+
+def ffn_fused_bwd(dy2: Ptrish, lddy2: int, dy2_rowmax: Ptrish, dy2_rowmax_n: int, rows: Ptrish, tile_group: Ptrish,
+                  ntiles: int, w2_image, w2_groups: int, w1_image, w1_groups: int, f: int, u: Ptrish, ldu: int,
+                  du: Ptrish, lddu: int, x1: Ptrish, ldx1: int, gamma: Ptrish, rstd: Ptrish, dx1: Ptrish, lddx1: int,
+                  dgamma: Ptrish, *, du_amax: Ptrish = None, dres: Ptrish = None, lddres: int = 0,
+                  dx_masked: Ptrish = None, lddxm: int = 0, accumulate_dgamma: bool = False, amax_out: Ptrish = None,
+                  rowabs_out: Ptrish = None, rowabs_n: int = 0, seed: int = 0, site: int = 0, drop: float = 0.0,
+                  tail: Tuple[int, int] = (1, 1), m_rows: int = 0, device=None) -> None:
+    """ot_ffn_fused_bwd: du = (dy2 @ W2[g]^T) * gelu'(u) and dx1 = norm2_bwd(du @ W1[g]^T) + dres [, dx_masked] for
+    rows of 128 floats in one launch (split mode; ``w2_image`` / ``w1_image``: the pair-form dgrad images as
+    ``(tensor, element offset)``; ``dy2_rowmax``: dy2's row maxima as the FFN2 dgrad launch's ``a_rowmax``).  ``du``
+    and ``du_amax`` are bit for bit that launch's; the epilogue operands are the FFN1 dgrad launch's."""
+    ws = workspace(size('ot_mixed_gemm_rms_workspace_size', ntiles, 128),
+                   device if device is not None else (dx1[0] if isinstance(dx1, tuple) else dx1).device)
+    a = _lib.FfnFusedBwdArgs(ctypes.sizeof(_lib.FfnFusedBwdArgs), ptr(dy2), lddy2, ptr(dy2_rowmax), int(dy2_rowmax_n),
+                             ptr(rows), ptr(tile_group), ntiles, ptr(w2_image), int(w2_groups), ptr(w1_image),
+                             int(w1_groups), f, ptr(u), ldu, ptr(du), lddu, ptr(du_amax), ptr(x1), ldx1, ptr(gamma),
+                             ptr(rstd), ptr(dres), lddres, ptr(dx1), lddx1, ptr(dx_masked), lddxm, ptr(dgamma),
+                             int(accumulate_dgamma), ptr(ws), ws.numel(), ptr(amax_out), ptr(rowabs_out),
+                             int(rowabs_n), seed & 0xFFFFFFFF, site, float(drop), tail[0], tail[1], _sel(tail))
+    ev = _probe.begin() if _probe is not None else None
+    call('ot_ffn_fused_bwd', ctypes.byref(a), stream())
+    if ev is not None:
+        M = m_rows or ntiles * 128
+        # algorithmic bytes: dy2, u, x1, dres in; du, dx1, dx_masked out (13 R at f = 512 with dropout)
+        _probe.end('mixed_gemm', 2.0 * M * 128 * f * 2, ev, f'ffn_fused_bwd M{M} f{f} drop{int(drop > 0)}',
+                   4.0 * M * 128 * (3 + (dres is not None) + (dx_masked is not None)) + 4.0 * M * f * 2
+                   + 4.0 * M * (1 + dy2_rowmax_n), 3)
+
+
 def split_images(base, desc_dev, ndesc, total_units, img) -> None:
     call('ot_split_images', ptr(base), ptr(desc_dev), ndesc, total_units, ptr(img), _prec(), stream())
 

@@ -539,9 +539,27 @@ class _Block(torch.autograd.Function):
         # does the FFN2 dgrad report dU's bound and row maxima?  (its whole-tile vector epilogue does)
         du_rep = fused2 or (((bounds is not None and not du_bf) or pw2 or pw1) and f % TILE == 0)
         b_du = out('du') if du_rep and not du_bf else None
-        rm_du = torch.empty(B * Kq, f // TILE, device=dev) if pw1 and du_rep else None
+        # split mode, d == 128, pair-form W2 / W1 dgrad images, float32 dU, the norm2 backward in the FFN1 dgrad's
+        # epilogue: both input gradients in one launch (ot_ffn_fused_bwd: dU is written for the W1 weight gradient but not
+        # read back, and its row maxima stay in registers)
+        ffn_bwd = (pw2 and pw1 and m.fuse_bwd and d == TILE and f % TILE == 0 and f <= K.FFN_FUSED_MAX_F
+                   and not du_bf and h is None and bool(K.ffn_fused_bwd_on()))
+        rm_du = torch.empty(B * Kq, f // TILE, device=dev) if pw1 and du_rep and not ffn_bwd else None
         rep_du = dict(amax_out=b_du, rowabs_out=rm_du, rowabs_n=f // TILE if rm_du is not None else 0)
-        if fused2:
+        if ffn_bwd:
+            dx1 = torch.empty(B * Kq, d, device=dev)
+            dyo = torch.empty(B * Kq, d, device=dev) if rate > 0 else dx1
+            rm_dyo = torch.empty(B * Kq, 1, device=dev) if pwo else None
+            b_dyo = out('dyo')
+            K.ffn_fused_bwd(dy2, d, pa2['a_rowmax'], pa2['a_rowmax_n'], mt['rows'][1], mt['tile_group'], nt,
+                            m.bimg(f'blk.{l}.w2', 'dgrad')[0], m.layout.images[(f'blk.{l}.w2', 'dgrad')][1],
+                            m.bimg(f'blk.{l}.w1', 'dgrad')[0], m.layout.images[(f'blk.{l}.w1', 'dgrad')][1], f,
+                            u, f, du, f, x1, d, m.p(f'blk.{l}.norm2'), rstd2, dx1, d, m.g(f'blk.{l}.norm2'),
+                            du_amax=b_du, dres=dx2, lddres=d, dx_masked=dyo if rate > 0 else None, lddxm=d,
+                            accumulate_dgamma=acc, amax_out=b_dyo, rowabs_out=rm_dyo,
+                            rowabs_n=1 if rm_dyo is not None else 0, seed=seed, site=2 * l, drop=rate, tail=tail,
+                            m_rows=maps['tail'].nrows, device=dev)
+        elif fused2:
             # d > 128: the FFN2 dgrad also emits rowdot[row][f-tile] = sum dU (U - b1) for the norm2 backward
             rowdot = torch.empty(B * Kq, f // TILE, device=dev)
             K.gemm_rms(OT_GEMM_NT, dy2, d, d, mt['rows'][1], m.p(f'blk.{l}.w2'), f * d, d, f, mt['tile_group'], nt,
@@ -559,7 +577,7 @@ class _Block(torch.autograd.Function):
             K.gemm_rms(OT_GEMM_NT, dy2, d, d, mt['rows'][1], m.p(f'blk.{l}.w2'), f * d, d, f, mt['tile_group'], nt, du,
                        f, mt['rows'][1], epi=OT_EPI_GELU_BWD, aux=u, ldaux=f, m_rows=maps['tail'].nrows, device=dev,
                        bimg=m.bimg(f'blk.{l}.w2', 'dgrad'), **rep_du, **pa2)
-        pa1 = a_row_bounds(pw1, du, f, B * Kq, f, rm_du)
+        pa1 = a_row_bounds(pw1, du, f, B * Kq, f, rm_du) if not ffn_bwd else {}
         a1n = x1n is not None and du_bf               # both operands bf16: the copy-staged weight gradient
         with m.side(x1n if a1n else x1, du, rstd2, *keep):
             K.wgrad(x1n if a1n else x1, d, mt['rows'][1], du, f, mt['rows'][1], d, f, mt, nct, G, m.g(f'blk.{l}.w1'),
@@ -567,12 +585,15 @@ class _Block(torch.autograd.Function):
                     a_xform=(OT_AX_BF16 if a1n else OT_AX_RMSNORM) | (OT_WG_D_BF16 if du_bf else 0),
                     accumulate=acc, device=dev, m_rows=maps['tail'].nrows, rowmap=maps['tail'], d_bound=b_du)
         # FFN1 dgrad -> norm2 backward + residual; emit mask(dx1) for the attention branch
-        dx1 = torch.empty(B * Kq, d, device=dev)
-        dyo = torch.empty(B * Kq, d, device=dev) if rate > 0 else dx1
         dx1_ep = m.fuse_bwd or rowdot is not None   # FFN1 dgrad -> norm2 backward in the epilogue, which reports on dyo
-        rm_dyo = torch.empty(B * Kq, (d + TILE - 1) // TILE, device=dev) if pwo and dx1_ep else None
-        b_dyo = out('dyo') if dx1_ep else None
-        if dx1_ep:
+        if not ffn_bwd:
+            dx1 = torch.empty(B * Kq, d, device=dev)
+            dyo = torch.empty(B * Kq, d, device=dev) if rate > 0 else dx1
+            rm_dyo = torch.empty(B * Kq, (d + TILE - 1) // TILE, device=dev) if pwo and dx1_ep else None
+            b_dyo = out('dyo') if dx1_ep else None
+        if ffn_bwd:
+            pass                                    # dx1 / dyo and their reports came from the fused launch above
+        elif dx1_ep:
             K.gemm_rms(OT_GEMM_NT, du, f, f, mt['rows'][1], m.p(f'blk.{l}.w1'), d * f, f, d, mt['tile_group'], nt,
                        dx1, d, mt['rows'][1], epi=OT_EPI_RMSNORM_BWD | (OT_EPI_DROPOUT if rate > 0 else 0),
                        a_xform=OT_AX_BF16 if du_bf else 0,
