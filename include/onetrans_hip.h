@@ -949,6 +949,35 @@ int ot_ns_bag_pool(const ot_ns_bag* bags, int nbags, int B, float* out, int64_t 
 int ot_ns_bag_grad_pack(const ot_ns_bag* bags, int nbags, int B, const float* dmat, int64_t ld, const float* coef,
                         int64_t* keys, float* grads, void* stream);
 
+/* ---- group-wise NS tokenizer (ns_group.hip) ------------------------------------------------------
+ * Paper eq. 6: the NS features are partitioned into G groups and group g goes through its own
+ * Dense(K_g -> d) to become NS token g; a grouped GEMM whose groups differ in K.  Every row b of the NS
+ * matrix A feeds all G groups, group g from the columns goff[g] .. goff[g+1]-1 and the rows of the same
+ * numbers of the group-major weight bank W [goff[G]][d]; bias is [G][d].
+ *   fwd         X[b*ldx + g*d + n]      = sum_k A[b*lda + goff[g]+k] * W[(goff[g]+k)*d + n] + bias[g*d + n]
+ *   bwd_input   dA[b*lda + goff[g]+k]   = sum_n D[b*ldd + g*d + n] * W[(goff[g]+k)*d + n]   (every column of
+ *               every group's range is written; columns of A outside the ranges are untouched)
+ *   bwd_weight  dW[(goff[g]+k)*d + n] (+)= sum_b A[b*lda + goff[g]+k] * D[b*ldd + g*d + n],
+ *               db[g*d + n] (+)= sum_b D[b*ldd + g*d + n]; row chunks write partial slabs into the workspace
+ *               (ot_ns_group_wgrad_workspace_size) and the slabs are added in chunk order: bitwise
+ *               reproducible, no float atomics.  accumulate != 0 adds onto dW / db.
+ * goff: DEVICE int32 [G+1], goff[0] = 0, strictly increasing (no alignment is assumed); the host passes G,
+ * ktot = goff[G] and kmax >= the largest K_g = goff[g+1] - goff[g].  goff is never read on the host: a range
+ * that is empty or leaves [0, ktot] is skipped on the device, so no table can send an access out of bounds.
+ * Arithmetic: exact f32, one fmaf per product in ascending order of the summed index, whatever the model's
+ * matmul precision.  Stream-ordered, no allocation, no host sync.
+ * B >= 1, G >= 1, d % 4 == 0 and 4 <= d <= 512, ktot <= 2^22, lda >= ktot, ldx / ldd >= G*d and a multiple
+ * of 4, W / bias / X / D / dW / db / workspace 16-byte aligned; anything else, or a null operand, returns
+ * OT_ERR_INVALID_ARG before any launch. */
+int ot_ns_group_fwd(const float* A, int64_t lda, const int32_t* goff, int G, int ktot, int kmax, const float* W,
+                    const float* bias, int B, int d, float* X, int64_t ldx, void* stream);
+int ot_ns_group_bwd_input(const float* D, int64_t ldd, const int32_t* goff, int G, int ktot, int kmax,
+                          const float* W, int B, int d, float* dA, int64_t lda, void* stream);
+size_t ot_ns_group_wgrad_workspace_size(int B, int G, int ktot, int d);
+int ot_ns_group_bwd_weight(const float* A, int64_t lda, const float* D, int64_t ldd, const int32_t* goff, int G,
+                           int ktot, int kmax, int B, int d, float* dW, float* db, int accumulate, void* workspace,
+                           size_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

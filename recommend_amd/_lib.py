@@ -240,6 +240,11 @@ SIGNATURES = {
     'ot_last_fold': (c_int, [c_int]),
     'ot_ns_bag_pool': (c_int, [P, c_int, c_int, P, I64, P, P]),
     'ot_ns_bag_grad_pack': (c_int, [P, c_int, c_int, P, I64, P, P, P, P]),
+    'ot_ns_group_fwd': (c_int, [P, I64, P, c_int, c_int, c_int, P, P, c_int, c_int, P, I64, P]),
+    'ot_ns_group_bwd_input': (c_int, [P, I64, P, c_int, c_int, c_int, P, c_int, c_int, P, I64, P]),
+    'ot_ns_group_wgrad_workspace_size': (c_size_t, [c_int, c_int, c_int, c_int]),
+    'ot_ns_group_bwd_weight': (c_int, [P, I64, P, I64, P, c_int, c_int, c_int, c_int, c_int, P, P, c_int, P,
+                                       c_size_t, P]),
 }
 
 # ABI notes (mirrors include/onetrans_hip.h): the modes/flags above; the device-side struct is

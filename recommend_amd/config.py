@@ -124,6 +124,12 @@ class OneTransConfig:
         # reference): a padding event is an ordinary token and nothing new is read
         self.seq_padding_mask = False
         self.seq_len_suffix = '_len'
+        # build: how the NS features become the L_NS non-sequence tokens (paper §3.2.1).  'auto' (the
+        # reference, eq. 7): one Dense(F_ns -> L_NS*d) cut into tokens.  'group' (eq. 6): ``ns_token_groups``, a list
+        # of num_ns_tokens lists of NS feature names that partition ns_feature_names(), and group g goes through its
+        # own Dense(F_g -> d) to become token g
+        self.ns_tokenizer = 'auto'
+        self.ns_token_groups: List[List[str]] = []
 
     # ------------------------------------------------------------------ helpers
     def to_dict(self) -> Dict:
@@ -338,6 +344,87 @@ def check_padding_mask(cfg: OneTransConfig) -> None:
                          "padding tokens (not implemented); use pyramid_select='tail'")
 
 
+def check_ns_tokenizer(cfg: OneTransConfig) -> None:
+    """``ns_tokenizer`` is 'auto' (reference: one Dense cut into tokens) or 'group' (one Dense per feature group);
+    'group' needs ``ns_token_groups``: num_ns_tokens non-empty lists of NS feature names, every name of
+    ``ns_feature_names()`` in exactly one of them."""
+    mode = getattr(cfg, 'ns_tokenizer', 'auto')
+    if mode not in ('auto', 'group'):
+        raise ValueError(f"unknown ns_tokenizer {mode!r}: expected 'auto' or 'group'")
+    if mode == 'auto':
+        return
+    groups = getattr(cfg, 'ns_token_groups', None)
+    if not groups:
+        raise ValueError("ns_tokenizer='group' needs ns_token_groups (num_ns_tokens lists of NS feature names)")
+    if len(groups) != cfg.num_ns_tokens:
+        raise ValueError(f'ns_token_groups has {len(groups)} groups, num_ns_tokens is {cfg.num_ns_tokens}')
+    names = cfg.ns_feature_names()
+    seen = {}
+    for g, members in enumerate(groups):
+        if isinstance(members, str) or not len(members):
+            raise ValueError(f'ns_token_groups[{g}] is empty (or not a list of names)')
+        for n in members:
+            if n not in names:
+                raise ValueError(f'ns_token_groups[{g}]: {n!r} is in none of the user / item / context feature lists')
+            if n in seen:
+                raise ValueError(f'ns_token_groups: feature {n!r} is in groups {seen[n]} and {g}')
+            seen[n] = g
+    missing = [n for n in names if n not in seen]
+    if missing:
+        raise ValueError(f'ns_token_groups: features {missing} are in no group')
+
+
+def ns_group_mode(cfg: OneTransConfig) -> bool:
+    return getattr(cfg, 'ns_tokenizer', 'auto') == 'group'
+
+
+def ns_group_layout(cfg: OneTransConfig) -> Dict:
+    """Rows of the group-major ``tok.ns.kernel`` [F_ns, d], which are also the columns of the NS matrix, under
+    ns_tokenizer='group'.  Inside a group the features follow concat order (``ns_feature_names()``),
+    ``ns_feature_width`` rows each; the groups are not padded (the kernels assume no alignment of a group's range).
+
+    * ``members``: the groups' features in that order; ``widths``: F_g per group.
+    * ``goff`` [G+1]: the groups' first rows, goff[G] = F_ns; ``col``: feature -> its first row / column."""
+    check_ns_tokenizer(cfg)
+    order = {n: i for i, n in enumerate(cfg.ns_feature_names())}
+    members = [sorted(g, key=order.__getitem__) for g in cfg.ns_token_groups]
+    goff, col, widths = [0], {}, []
+    for g in members:
+        r = goff[-1]
+        for n in g:
+            col[n] = r
+            r += cfg.ns_feature_width(n)
+        widths.append(r - goff[-1])
+        goff.append(r)
+    return {'members': members, 'widths': widths, 'goff': goff, 'col': col}
+
+
+def even_ns_groups(cfg: OneTransConfig) -> List[List[str]]:
+    """``ns_feature_names()`` cut, in concat order, into num_ns_tokens contiguous runs of near-equal column width: run
+    g ends at the feature whose end column is nearest to (g+1)/L of the total, every run keeping at least one
+    feature.  Needs at least num_ns_tokens features."""
+    names = cfg.ns_feature_names()
+    L = cfg.num_ns_tokens
+    if len(names) < L:
+        raise ValueError(f'even_ns_groups: {len(names)} NS features cannot fill {L} groups')
+    ends = []
+    c = 0
+    for n in names:
+        c += cfg.ns_feature_width(n)
+        ends.append(c)
+    total, groups, start = c, [], 0
+    for g in range(L):
+        if g == L - 1:
+            stop = len(names)
+        else:
+            lo, hi = start + 1, len(names) - (L - 1 - g)          # leave a feature for every later run
+            target = total * (g + 1) / L
+            stop = min(range(lo, hi + 1), key=lambda i: (abs(ends[i - 1] - target), i))
+        groups.append(names[start:stop])
+        start = stop
+    return groups
+
+
 BAG_POOLINGS = ('sum', 'mean')
 
 
@@ -429,4 +516,5 @@ def algorithmic_flops_per_sample(cfg: OneTransConfig, seq_lens: List[int], f_ns:
 
 __all__ = ['OneTransConfig', 'OneTransSmallConfig', 'OneTransLargeConfig', 'get_model_config',
            'dense_optimizer_spec', 'DEFAULT_CONFIG', 'workload_config', 'algorithmic_flops_per_sample',
-           'CRITEO_CARDINALITIES', 'check_bag_features']
+           'CRITEO_CARDINALITIES', 'check_bag_features', 'check_ns_tokenizer', 'even_ns_groups', 'ns_group_layout',
+           'ns_group_mode']

@@ -891,6 +891,40 @@ def ns_bag_grad_pack(descs, nbags: int, B: int, dmat, ld: int, coef, keys, grads
         _probe.end('embedding', 0.0, ev)
 
 
+def ns_group_fwd(A: Ptrish, lda: int, goff: Ptrish, G: int, ktot: int, kmax: int, W: Ptrish, bias: Ptrish, B: int,
+                 d: int, X: Ptrish, ldx: int) -> None:
+    """ot_ns_group_fwd: NS token g of row b = A[b, goff[g]:goff[g+1]] @ W[goff[g]:goff[g+1]] + bias[g] (exact f32).
+    ``goff``: device int32 [G+1]; ``ktot`` = goff[G], ``kmax`` >= the widest group."""
+    ev = _probe.begin() if _probe is not None else None
+    call('ot_ns_group_fwd', ptr(A), lda, ptr(goff), G, ktot, kmax, ptr(W), ptr(bias), B, d, ptr(X), ldx, stream())
+    if ev is not None:
+        _probe.end('mixed_gemm', 2.0 * B * ktot * d, ev, f'ns_group_fwd M{B} K{ktot} N{d} G{G}',
+                   4.0 * (B * ktot + ktot * d + B * G * d))
+
+
+def ns_group_bwd_input(D: Ptrish, ldd: int, goff: Ptrish, G: int, ktot: int, kmax: int, W: Ptrish, B: int, d: int,
+                       dA: Ptrish, lda: int) -> None:
+    """ot_ns_group_bwd_input: dA[b, goff[g]:goff[g+1]] = D[b, g] @ W[goff[g]:goff[g+1]]^T."""
+    ev = _probe.begin() if _probe is not None else None
+    call('ot_ns_group_bwd_input', ptr(D), ldd, ptr(goff), G, ktot, kmax, ptr(W), B, d, ptr(dA), lda, stream())
+    if ev is not None:
+        _probe.end('mixed_gemm', 2.0 * B * ktot * d, ev, f'ns_group_bwd_input M{B} K{ktot} N{d} G{G}',
+                   4.0 * (B * ktot + ktot * d + B * G * d))
+
+
+def ns_group_bwd_weight(A: Ptrish, lda: int, D: Ptrish, ldd: int, goff: Ptrish, G: int, ktot: int, kmax: int, B: int,
+                        d: int, dW: Ptrish, db: Ptrish, accumulate: bool = False, device=None) -> None:
+    """ot_ns_group_bwd_weight: dW[goff[g]:goff[g+1]] (+)= A[:, goff[g]:goff[g+1]]^T @ D[:, g], db[g] (+)= sum_b D[b, g]
+    (deterministic: partial slabs per row chunk, added in chunk order)."""
+    ws = workspace(size('ot_ns_group_wgrad_workspace_size', B, G, ktot, d), device)
+    ev = _probe.begin() if _probe is not None else None
+    call('ot_ns_group_bwd_weight', ptr(A), lda, ptr(D), ldd, ptr(goff), G, ktot, kmax, B, d, ptr(dW), ptr(db),
+         int(accumulate), ptr(ws), ws.numel(), stream())
+    if ev is not None:
+        _probe.end('mixed_gemm', 2.0 * B * ktot * d, ev, f'ns_group_bwd_weight M{B} K{ktot} N{d} G{G}',
+                   4.0 * (B * ktot + B * G * d + (ktot + G) * d))
+
+
 def seq_time_descs(seqs):
     """The host descriptor array of ``seq_time_rows``: ``seqs`` = [(times, stride_b, L, map_off)], ``times`` a device
     int64 tensor (or (tensor, element offset)).  Build it once for buffers that persist (OneTransModel's plan)."""

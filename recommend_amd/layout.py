@@ -20,7 +20,7 @@ from typing import Callable, Dict, List, Sequence, Tuple
 
 import numpy as np
 
-from .config import OneTransConfig
+from .config import OneTransConfig, ns_group_layout, ns_group_mode
 from .params import dense_param_shapes, keras_variables
 
 TILE = 128
@@ -58,6 +58,12 @@ class FlatLayout:
     def __init__(self, cfg: OneTransConfig, f_ns: int, pair_dgrad: bool = False):
         self.f_ns, self.pair_dgrad = f_ns, pair_dgrad
         self.f_pad = max(4, round_up(f_ns, 4))
+        # ns_tokenizer='group': tok.ns.kernel is [f_pad, d], group-major (rows goff[g] .. goff[g+1] are group g's
+        # Dense, unpadded; the rows f_ns .. f_pad stay zero as in the auto-split bank); the grouped kernels read the
+        # bank as it is stored
+        self.ns_groups = ns_group_layout(cfg) if ns_group_mode(cfg) else None
+        if self.ns_groups is not None and self.ns_groups['goff'][-1] != f_ns:
+            raise ValueError(f"f_ns={f_ns}, the groups of ns_token_groups hold {self.ns_groups['goff'][-1]} columns")
         self.shapes = dense_param_shapes(cfg, self.f_pad)
         self.offsets: Dict[str, int] = {}
         off = 0
@@ -77,6 +83,8 @@ class FlatLayout:
         self.gemm_banks = {'tok.ns.kernel': (1, self.f_pad, cfg.num_ns_tokens * d),
                            'tok.seq.kernel': (nseq, cfg.seq_feature_dim, d),
                            'head.w1': (T, d, d // 2)}
+        if self.ns_groups is not None:           # no transposed shadow and no plane images for the grouped bank
+            del self.gemm_banks['tok.ns.kernel']
         for l in range(cfg.num_layers):
             G = cfg.num_groups
             self.gemm_banks.update({f'blk.{l}.wqkv': (G, d, 3 * d), f'blk.{l}.wo': (1, d, d),

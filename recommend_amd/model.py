@@ -30,12 +30,13 @@ from . import kernels as K
 from ._lib import (OT_AX_BF16, OT_AX_BF16_RMSNORM, OT_AX_GELU, OT_AX_RMSNORM, OT_EPI_ACCUMULATE, OT_EPI_AUX_BF16, OT_EPI_BIAS,
                    OT_EPI_C_BF16, OT_EPI_DROPOUT, OT_EPI_GELU_BWD, OT_EPI_RESIDUAL, OT_EPI_RMSNORM_BWD,
                    OT_EPI_ROW_RSTD, OT_EPI_ROWDOT, OT_GEMM_NN, OT_GEMM_NT, OT_WG_D_BF16, NS_FIELD_BYTES)
-from .config import (OneTransConfig, check_bag_features, check_padding_mask, check_pyramid_select, check_seq_fusion,
-                     get_model_config)
+from .config import (OneTransConfig, check_bag_features, check_ns_tokenizer, check_padding_mask, check_pyramid_select,
+                     check_seq_fusion, get_model_config)
 from .layout import TILE, FlatLayout, RowMap, build_map, head_map, identity_map, layer_maps, round_up
 from .params import init_params, ns_table_offsets
 
 RMS_EPS = 1e-6   # RMSNorm eps, model.py:14
+NS_GROUPS_KEY = '__ns_token_groups__'   # save_weights: the groups of a group-wise NS tokenizer (JSON), next to the banks
 
 
 # =============================================================================== autograd ops
@@ -55,10 +56,15 @@ class _Tokenize(torch.autograd.Function):
                 K.ns_assemble(plan['ns_desc'], plan['ns_desc_n'], m.tables.get('emb.ns'), B, nsm, m.layout.f_pad)
             if plan['n_bags'] > 0:                              # multi-valued features: pooled rows, same matrix
                 K.ns_bag_pool(plan['bag_descs'], plan['n_bags'], B, nsm, m.layout.f_pad, plan['bag_coef'])
-            mp = plan['ns_map'].to(dev)
-            K.gemm(OT_GEMM_NT, nsm, m.layout.f_pad, m.layout.f_pad, mp['rows'][0], m.pT('tok.ns.kernel'), 0,
-                   m.layout.f_pad, m.cfg_Lnsd, mp['tile_group'], plan['ns_map'].ntiles, (x0, L_S * d), L0 * d,
-                   mp['rows'][0], bias=m.p('tok.ns.bias'), epi=OT_EPI_BIAS, m_rows=B, bimg=m.bimg('tok.ns.kernel'))
+            if m.ns_goff is not None:                           # one Dense(F_g -> d) per feature group (paper eq. 6)
+                K.ns_group_fwd(nsm, m.layout.f_pad, m.ns_goff, m.config.num_ns_tokens, m.layout.f_pad, m.ns_kmax,
+                               m.p('tok.ns.kernel'), m.p('tok.ns.bias'), B, d, (x0, L_S * d), L0 * d)
+            else:
+                mp = plan['ns_map'].to(dev)
+                K.gemm(OT_GEMM_NT, nsm, m.layout.f_pad, m.layout.f_pad, mp['rows'][0], m.pT('tok.ns.kernel'), 0,
+                       m.layout.f_pad, m.cfg_Lnsd, mp['tile_group'], plan['ns_map'].ntiles, (x0, L_S * d), L0 * d,
+                       mp['rows'][0], bias=m.p('tok.ns.bias'), epi=OT_EPI_BIAS, m_rows=B,
+                       bimg=m.bimg('tok.ns.kernel'))
         else:                                                   # model.py:249-251
             x0.view(B, L0, d)[:, L_S:].zero_()
         # ---- S tokens: per-sequence Dense(d) on gathered item rows (model.py:262-265)
@@ -94,14 +100,24 @@ class _Tokenize(torch.autograd.Function):
         if plan['ns_fields'] > 0:
             mp = plan['ns_map'].to(dev)
             nsm = plan['nsmat']
-            K.wgrad(nsm, m.layout.f_pad, mp['rows'][0], (dx0, L_S * d), L0 * d, mp['rows'][0], m.layout.f_pad,
-                    m.cfg_Lnsd, mp, plan['ns_map'].chunks.shape[0], 1, m.g('tok.ns.kernel'), 0, m.g('tok.ns.bias'),
-                    0, accumulate=acc, device=dev, m_rows=B, rowmap=plan['ns_map'])
+            grouped = m.ns_goff is not None
+            if grouped:
+                K.ns_group_bwd_weight(nsm, m.layout.f_pad, (dx0, L_S * d), L0 * d, m.ns_goff, m.config.num_ns_tokens,
+                                      m.layout.f_pad, m.ns_kmax, B, d, m.g('tok.ns.kernel'), m.g('tok.ns.bias'),
+                                      accumulate=acc, device=dev)
+            else:
+                K.wgrad(nsm, m.layout.f_pad, mp['rows'][0], (dx0, L_S * d), L0 * d, mp['rows'][0], m.layout.f_pad,
+                        m.cfg_Lnsd, mp, plan['ns_map'].chunks.shape[0], 1, m.g('tok.ns.kernel'), 0,
+                        m.g('tok.ns.bias'), 0, accumulate=acc, device=dev, m_rows=B, rowmap=plan['ns_map'])
             if plan['n_sparse'] > 0 or plan['n_bags'] > 0:
                 dns = torch.empty(B, m.layout.f_pad, device=dev)
-                K.gemm(OT_GEMM_NT, (dx0, L_S * d), L0 * d, m.cfg_Lnsd, mp['rows'][0], m.p('tok.ns.kernel'), 0,
-                       m.cfg_Lnsd, m.layout.f_pad, mp['tile_group'], plan['ns_map'].ntiles, dns, m.layout.f_pad,
-                       mp['rows'][0], m_rows=B)
+                if grouped:
+                    K.ns_group_bwd_input((dx0, L_S * d), L0 * d, m.ns_goff, m.config.num_ns_tokens, m.layout.f_pad,
+                                         m.ns_kmax, m.p('tok.ns.kernel'), B, d, dns, m.layout.f_pad)
+                else:
+                    K.gemm(OT_GEMM_NT, (dx0, L_S * d), L0 * d, m.cfg_Lnsd, mp['rows'][0], m.p('tok.ns.kernel'), 0,
+                           m.cfg_Lnsd, m.layout.f_pad, mp['tile_group'], plan['ns_map'].ntiles, dns, m.layout.f_pad,
+                           mp['rows'][0], m_rows=B)
                 e = m.config.ns_embedding_dim
                 # one (keys, grads) pair per table: the single-id fields' B entries each, then every slot of the
                 # emb.ns bags; the emb.seq_item bags' slots are a second entry of that table (the optimizer joins
@@ -884,6 +900,7 @@ class OneTransModel(nn.Module):
         check_seq_fusion(cfg)
         check_bag_features(cfg)
         check_padding_mask(cfg)
+        check_ns_tokenizer(cfg)
         self.padding_mask = bool(getattr(cfg, 'seq_padding_mask', False))
         self.time_fusion = getattr(cfg, 'seq_fusion', 'sep') == 'time'
         # compute_dtype (build knob): 'fp32' (the reference's arithmetic: split or f32 GEMMs, ``matmul`` below),
@@ -918,6 +935,17 @@ class OneTransModel(nn.Module):
         # maxima from their producers; ONETRANS_PAIR_DGRAD=0: the six-product split)
         self.layout = FlatLayout(cfg, self.f_ns, pair_dgrad=os.environ.get('ONETRANS_PAIR_DGRAD', '1') != '0')
         self.cfg_Lnsd = cfg.num_ns_tokens * cfg.hidden_dim
+        # ns_tokenizer='group' (DESIGN.md §7g): the groups' first columns of the NS matrix = first rows of
+        # tok.ns.kernel, on the device for the grouped kernels (ot_ns_group_*), and the widest group
+        self.ns_goff, self.ns_kmax = None, 0
+        if self.layout.ns_groups is not None:
+            if cfg.hidden_dim % 4 or cfg.hidden_dim > 512:
+                raise ValueError(f"ns_tokenizer='group' needs hidden_dim % 4 == 0 and <= 512, got {cfg.hidden_dim}")
+            # (the last group's range runs on over the bank's padding rows f_ns .. f_pad: zero columns of the NS
+            # matrix and zero rows of the bank, so nothing changes but that their gradient rows are written, as zeros)
+            gp = self.layout.ns_groups['goff'][:-1] + [self.layout.f_pad]
+            self.ns_goff = torch.tensor(gp, dtype=torch.int32, device=self.device)
+            self.ns_kmax = max(b - a for a, b in zip(gp[:-1], gp[1:]))
         self.flat = nn.Parameter(torch.zeros(self.layout.total, device=self.device))
         self.flat.grad = torch.zeros_like(self.flat)
         self.flatT = torch.zeros(self.layout.total, device=self.device)     # transposed GEMM weight shadow
@@ -1100,12 +1128,32 @@ class OneTransModel(nn.Module):
                     continue
                 dst = self.p(name)
                 src = torch.as_tensor(np.asarray(arr), dtype=torch.float32)
+                if name in ('tok.ns.kernel', 'tok.ns.bias'):
+                    self._check_ns_bank(name, tuple(src.shape))
                 if name == 'tok.ns.kernel' and src.shape[0] != dst.shape[0]:
                     dst.zero_()
                     dst[:src.shape[0]].copy_(src)
                 else:
                     dst.copy_(src.reshape(dst.shape))
         self.refresh_shadow()
+
+    def _check_ns_bank(self, name: str, shape) -> None:
+        """A loaded NS tokenizer bank must have this model's tokenizer mode: the auto-split bank is
+        [F_ns, L_NS*d] / [L_NS*d], the grouped one [F_ns, d] / [L_NS, d]."""
+        cfg = self.config
+        L, d = cfg.num_ns_tokens, cfg.hidden_dim
+        if self.layout.ns_groups is not None:
+            want = ('%d or %d' % (self.f_ns, self.layout.f_pad), d) if name == 'tok.ns.kernel' else (L, d)
+            ok = (len(shape) == 2 and shape[0] in (self.f_ns, self.layout.f_pad) and shape[1] == d
+                  if name == 'tok.ns.kernel' else shape == want)
+        else:
+            want = ('<= %d' % self.layout.f_pad, L * d) if name == 'tok.ns.kernel' else (L * d,)
+            ok = (len(shape) == 2 and shape[0] <= self.layout.f_pad and shape[1] == L * d
+                  if name == 'tok.ns.kernel' else int(np.prod(shape)) == L * d)
+        if not ok:
+            raise ValueError(f"{name}: loaded shape {shape} is not the {want} of ns_tokenizer="
+                             f"{getattr(cfg, 'ns_tokenizer', 'auto')!r}: the weights were saved with another NS "
+                             'tokenizer mode or other feature groups')
 
     def _table_shape(self, name: str):
         cfg = self.config
@@ -1470,11 +1518,16 @@ class OneTransModel(nn.Module):
             plan['dense_buf'] = torch.zeros(B, max(1, len(dense_names)), device=dev)
             plan['ids_buf'] = torch.zeros(B, max(1, len(sparse_names)), dtype=torch.int64, device=dev)
             # descriptors: sparse fields first (ot_ns_grad_pack packs the first n_sparse)
-            col = {}
-            c = 0
-            for n in ns_present:
-                col[n] = c
-                c += cfg.ns_feature_width(n)
+            if self.layout.ns_groups is not None:
+                # group mode: every configured feature owns fixed columns inside its group's range (group-major,
+                # following goff); a feature absent from the batch leaves its columns zero
+                col = self.layout.ns_groups['col']
+            else:
+                col = {}
+                c = 0
+                for n in ns_present:
+                    col[n] = c
+                    c += cfg.ns_feature_width(n)
             recs = np.zeros(max(1, plan['ns_desc_n']),
                             dtype=np.dtype([('dense', '<u8'), ('ids', '<u8'), ('row_offset', '<i8'),
                                             ('stride', '<i8'), ('col', '<i4'), ('width', '<i4')]))
@@ -1677,6 +1730,8 @@ class OneTransModel(nn.Module):
         """Counterpart of model.save_weights (train.py:286): one .npz of named banks.  Collective when a
         table is row-sharded (every rank calls it; the gathered table is written by rank 0 only)."""
         params = self.param_dict()
+        if self.layout.ns_groups is not None:                 # which feature owns which rows of tok.ns.kernel
+            params[NS_GROUPS_KEY] = np.array(json.dumps(self.layout.ns_groups['members']))
         if self.sharded and self._rank() != 0:
             return
         os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
@@ -1690,7 +1745,16 @@ class OneTransModel(nn.Module):
     def load_weights(self, path: str) -> None:
         """Counterpart of model.load_weights (train.py:332)."""
         with np.load(path, allow_pickle=False) as z:
-            self.load_param_dict({k: z[k] for k in z.files})
+            params = {k: z[k] for k in z.files}
+        saved = params.pop(NS_GROUPS_KEY, None)
+        mine = self.layout.ns_groups['members'] if self.layout.ns_groups is not None else None
+        saved = json.loads(str(saved)) if saved is not None else None
+        if saved != mine:
+            raise ValueError(f'{path}: the weights were saved with '
+                             + ("ns_tokenizer='auto'" if saved is None else f"ns_tokenizer='group', groups {saved}")
+                             + ', this model has '
+                             + ("ns_tokenizer='auto'" if mine is None else f"ns_tokenizer='group', groups {mine}"))
+        self.load_param_dict(params)
 
 
 def create_onetrans_model(model_type: str = 'default', device=None) -> OneTransModel:

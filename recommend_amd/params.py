@@ -8,6 +8,9 @@ name                   shape                            reference variable(s)
 =====================  ===============================  ==============================================
 tok.ns.kernel          [F_ns, L_NS*d]                   Tokenizer.ns_tokenizer Dense (model.py:211-214)
 tok.ns.bias            [L_NS*d]                         "
+  (ns_tokenizer         [F_ns, d], [L_NS, d]             build extension (paper eq. 6): one Dense(F_g -> d) per feature
+   = 'group')                                           group, the kernels stacked group-major (rows goff[g] ..
+                                                        goff[g+1], config.ns_group_layout), one bias row per group)
 tok.seq.kernel         [n_seq, E, d]                    Tokenizer.seq_projections[i] (model.py:217-219)
 tok.seq.bias           [n_seq, d]                       "
 tok.sep                [1, d]                           Tokenizer.sep_embedding (model.py:222)
@@ -37,7 +40,7 @@ from typing import Dict, List, Tuple
 
 import numpy as np
 
-from .config import OneTransConfig
+from .config import OneTransConfig, ns_group_layout, ns_group_mode
 
 
 def _glorot(rng: np.random.Generator, fan_in: int, fan_out: int) -> np.ndarray:
@@ -52,9 +55,13 @@ def dense_param_shapes(cfg: OneTransConfig, f_ns: int) -> Dict[str, Tuple[int, .
     nseq = len(cfg.feature_config['sequence_features'])
     shapes = {
         'tok.ns.kernel': (f_ns, L * d), 'tok.ns.bias': (L * d,),
+    }
+    if ns_group_mode(cfg):
+        shapes = {'tok.ns.kernel': (f_ns, d), 'tok.ns.bias': (L, d)}
+    shapes.update({
         'tok.seq.kernel': (nseq, E, d), 'tok.seq.bias': (nseq, d),
         'tok.sep': (1, d),
-    }
+    })
     for l in range(cfg.num_layers):
         shapes.update({
             f'blk.{l}.norm1': (d,), f'blk.{l}.norm2': (d,),
@@ -97,8 +104,15 @@ def init_params(cfg: OneTransConfig, f_ns: int, seed: int = 0, perturb: bool = F
     E = cfg.seq_feature_dim
     nseq = len(cfg.feature_config['sequence_features'])
     P: Dict[str, np.ndarray] = {}
-    P['tok.ns.kernel'] = _glorot(rng, f_ns, L * d)
-    P['tok.ns.bias'] = np.zeros(L * d)
+    if ns_group_mode(cfg):                                      # one Dense(F_g -> d) per group, in group order
+        widths = ns_group_layout(cfg)['widths']
+        if sum(widths) != f_ns:
+            raise ValueError(f'init_params: f_ns={f_ns}, the groups of ns_token_groups hold {sum(widths)} columns')
+        P['tok.ns.kernel'] = np.concatenate([_glorot(rng, w, d) for w in widths])
+        P['tok.ns.bias'] = np.zeros((L, d))
+    else:
+        P['tok.ns.kernel'] = _glorot(rng, f_ns, L * d)
+        P['tok.ns.bias'] = np.zeros(L * d)
     P['tok.seq.kernel'] = np.stack([_glorot(rng, E, d) for _ in range(nseq)])
     P['tok.seq.bias'] = np.zeros((nseq, d))
     P['tok.sep'] = rng.uniform(-0.05, 0.05, size=(1, d))       # Keras Embedding init
@@ -160,9 +174,16 @@ def keras_variables(cfg: OneTransConfig, shapes: Dict[str, Tuple[int, ...]],
         cols = shp[-1]
         out.append((name, 0, n // cols, cols, cols))
 
-    F = shapes['tok.ns.kernel'][0] if f_ns is None else f_ns      # real rows (bank may be padded)
-    out.append(('tok.ns.kernel', 0, F, shapes['tok.ns.kernel'][1], shapes['tok.ns.kernel'][1]))
-    whole('tok.ns.bias')
+    if ns_group_mode(cfg):
+        # each group's Dense is its own pair of Keras variables (the bank's padding rows past F_ns belong to no unit)
+        lay = ns_group_layout(cfg)
+        for g, w in enumerate(lay['widths']):
+            out.append(('tok.ns.kernel', lay['goff'][g] * d, w, d, d))
+            out.append(('tok.ns.bias', g * d, 1, d, d))
+    else:
+        F = shapes['tok.ns.kernel'][0] if f_ns is None else f_ns      # real rows (bank may be padded)
+        out.append(('tok.ns.kernel', 0, F, shapes['tok.ns.kernel'][1], shapes['tok.ns.kernel'][1]))
+        whole('tok.ns.bias')
     nseq, E, _ = shapes['tok.seq.kernel']
     for i in range(nseq):
         out.append(('tok.seq.kernel', i * E * d, E, d, d))
