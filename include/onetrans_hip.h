@@ -85,6 +85,9 @@ extern "C" {
 /* ot_mixed_gemm_wgrad: or'ed into a_xform, D holds bf16 values (uint16 bits, ldd in elements; 8-B aligned
  * rows; OT_MATMUL_BF16 / split modes) — dU stored by OT_EPI_C_BF16 */
 #define OT_WG_D_BF16 8
+/* ot_mixed_gemm_wgrad_keep: or'ed into a_xform, D is the gradient before a dropout mask and the call's keep bits
+ * select and scale it at staging time */
+#define OT_WG_D_KEEPBITS 16
 
 int ot_version(void);
 const char* ot_get_last_error_string(void);
@@ -219,6 +222,20 @@ int ot_mixed_gemm_wgrad_ex(const float* A, int64_t lda, const int32_t* a_rows, i
                            float* dW, int64_t dw_gstride, float* db, int64_t db_gstride,
                            int accumulate, void* workspace, size_t ws_bytes, const float* a_bound,
                            const float* d_bound, int precision, void* stream);
+
+/* ot_mixed_gemm_wgrad_ex's pair form with the GELU prologue (a_xform OT_AX_GELU | OT_WG_D_KEEPBITS, split mode,
+ * N % 128 == 0) on D' = keep ? D * d_scale : 0: D holds the gradient before a dropout mask, keep [d_row][ldkeep]
+ * uint32 the rows' keep bits in column order (bit n % 32 of word n / 32; ot_ffn_fused_bwd_mask's keep_out), d_scale
+ * 1 / (1 - rate).  d_bound: >= max |D|, before the mask (the kernel multiplies it by d_scale).  dW and db equal the
+ * call on a materialised D' whose d_bound has the scale of d_bound * d_scale, bit for bit.  ldkeep % 4 == 0, keep
+ * 16-B aligned. */
+int ot_mixed_gemm_wgrad_keep(const float* A, int64_t lda, const int32_t* a_rows, int a_xform,
+                             const float* D, int64_t ldd, const int32_t* d_rows, int K, int N,
+                             const int32_t* chunks, int nchunks, const int32_t* gchunk, int ngroups,
+                             float* dW, int64_t dw_gstride, float* db, int64_t db_gstride,
+                             int accumulate, void* workspace, size_t ws_bytes, const float* a_bound,
+                             const float* d_bound, const uint32_t* keep, int64_t ldkeep, float d_scale,
+                             int precision, void* stream);
 
 /* Transposed weight shadow for the forward GEMMs (NT staging reads k-contiguous rows):
  * dst[g][n][k] = src[g][k][n] per bank; banks_dev: [nbanks][6] int64 {src_off, dst_off, G, K, N,
@@ -362,6 +379,21 @@ int ot_ffn_fused_bwd(const ot_ffn_fused_bwd_args* args, void* stream);
  * Process-wide; on = -1 only queries; returns the previous setting.  The library only keeps the setting: the host
  * layer reads it. */
 int ot_ffn_fused_bwd_on(int on);
+/* ot_ffn_fused_bwd with the FFN dropout's backward inside it (drop_rate > 0): args->dy2 is dx2, the gradient before
+ * the mask, and args->dy2_rowmax bounds |dx2| per row (the kernel multiplies the bound by 1 / (1 - drop_rate)).  The
+ * kernel forms dy2 = keep ? dx2 / (1 - drop_rate) : 0 at fragment time, the mask that ot_dropout_apply_ex(dx2, seed,
+ * mask_site, drop_rate, tail map) applies, with the same f32 multiply: given row bounds with the scale of that pass's
+ * row maxima, every output equals {ot_dropout_apply_ex, ot_ffn_fused_bwd on its dy2} bit for bit.  (args->site stays
+ * the site of dx_masked.)  keep_out: [row][ldkeep] uint32, the row's 128 keep bits in column order (bit c % 32 of
+ * word c / 32), written for the rows the map names: the D mask of the W2 weight gradient (ot_mixed_gemm_wgrad_keep).
+ * ldkeep % 4 == 0, keep_out 16-B aligned. */
+int ot_ffn_fused_bwd_mask(const ot_ffn_fused_bwd_args* args, uint32_t mask_site, uint32_t* keep_out, int64_t ldkeep,
+                          void* stream);
+/* Whether the model's block backward, where it takes ot_ffn_fused_bwd under dropout, masks dx2 inside that kernel and
+ * inside the W2 weight gradient (1, default: no dropout pass, no dy2) or runs the dropout pass first (0); the
+ * environment variable ONETRANS_BWD_MASK_FUSED (0 / 1) sets the process's initial value.  Process-wide; on = -1 only queries;
+ * returns the previous setting.  The library only keeps the setting: the host layer reads it. */
+int ot_bwd_mask_fused(int on);
 
 /* ---- causal attention with a query tail (attention.hip) ----------------------------------
  * Replaces model.py:100-114 (einsum QK^T/sqrt(hd), band_part mask with -1e9, softmax, einsum PV)

@@ -26,6 +26,7 @@ OT_ATTN_DQKV_BF16 = 1
 OT_ATTN_QKV_BF16 = 2
 OT_ATTN_DQ_PART_BF16 = 4
 OT_WG_D_BF16 = 8
+OT_WG_D_KEEPBITS = 16
 OT_MATMUL_F32, OT_MATMUL_SPLIT_BF16, OT_MATMUL_BF16 = 0, 1, 2
 OT_FP8_DEQUANT, OT_FP8_TWO_TERM = 1, 2
 OT_RANK_SUM, OT_RANK_PRODUCT = 0, 1
@@ -120,6 +121,8 @@ SIGNATURES = {
                                     I64, P, I64, c_int, P, c_size_t, c_int, P]),
     'ot_mixed_gemm_wgrad_ex': (c_int, [P, I64, P, c_int, P, P, P, I64, P, c_int, c_int, P, c_int, P, c_int, P,
                                        I64, P, I64, c_int, P, c_size_t, P, P, c_int, P]),
+    'ot_mixed_gemm_wgrad_keep': (c_int, [P, I64, P, c_int, P, I64, P, c_int, c_int, P, c_int, P, c_int, P, I64, P,
+                                         I64, c_int, P, c_size_t, P, P, P, I64, c_float, c_int, P]),
     'ot_transpose_banks': (c_int, [P, P, P, c_int, I64, P]),
     'ot_mixed_gemm_img': (c_int, [c_int, P, I64, c_int, P, c_int, P, P, P, I64, I64, c_int, P, c_int, P, I64,
                                   P, I64, P, c_int, P, I64, c_int, P, I64, c_uint32, c_uint32, c_float, c_int,
@@ -137,6 +140,8 @@ SIGNATURES = {
     'ot_ffn_fused': (c_int, [c_int]),
     'ot_ffn_fused_bwd': (c_int, [P, P]),
     'ot_ffn_fused_bwd_on': (c_int, [c_int]),
+    'ot_ffn_fused_bwd_mask': (c_int, [P, c_uint32, P, I64, P]),
+    'ot_bwd_mask_fused': (c_int, [c_int]),
     'ot_split_images': (c_int, [P, P, c_int, I64, P, c_int, P]),
     'ot_attn_fwd': (c_int, [P, I64, c_int, c_int, c_int, c_int, P, c_int, P, P, c_int, P]),
     'ot_attn_fwd_fp8_workspace_size': (c_size_t, [c_int, c_int, c_int, c_int]),

@@ -334,8 +334,9 @@ static std::atomic<int> g_ffn_fused{ffn_fused_initial()};
 // not divide by three, so the ring position is carried (a scalar), not derived from the stage index.  The wait after
 // the dU stores (a chunk's first GEMM2 stage) and the last one are vmcnt(0).
 constexpr int FB_TAB_OFF = FF_TAB_OFF;                      // f column factors of W2's image, 128 of W1's
-static_assert(FB_TAB_OFF + (FF_MAX_F + GT) * 4 <= 80 * 1024, "fused FFN backward LDS");
-constexpr int ffn_bwd_lds(int f) { return FB_TAB_OFF + (f + GT) * 4; }
+constexpr int FB_KEEP_BYTES = GT * (GT / 8);                // the mask mode's keep bits: 16 B per row, after the factors
+static_assert(FB_TAB_OFF + (FF_MAX_F + GT) * 4 + FB_KEEP_BYTES <= 80 * 1024, "fused FFN backward LDS");
+constexpr int ffn_bwd_lds(int f, bool mask = false) { return FB_TAB_OFF + (f + GT) * 4 + (mask ? FB_KEEP_BYTES : 0); }
 
 struct FfnBwdArgs {
   GemmArgs e;                         // FFN1 dgrad's epilogue operands; A / lda / in_rows / a_rowmax: dy2 and its maxima
@@ -345,9 +346,17 @@ struct FfnBwdArgs {
   float* du; int64_t lddu;
   float* du_amax;
   int f;
+  // MASKA: A is dx2, the gradient before the FFN dropout's mask; dy2 = keep ? dx2 * e.drop_scale : 0 is formed at
+  // fragment time from (e.seed, a_site, e.drop_thr, e's tail map), and the keep bits go to keep_out
+  uint32_t a_site; uint32_t* keep_out; int64_t ldkeep;
 };
 
-template <int EPIT>
+// MASKA (ot_ffn_fused_bwd_mask): the stage copies stay raw copies of the A rows.  In the prologue each lane hashes the
+// 64 columns of its row that it will read (k = 16 kt + 8 h + e: byte 2 kt + h of the row's 16, so the table is the
+// row's bits in column order) into an LDS table; a k-step reads its byte back and selects (nothing more is held across
+// the loop: the kernel sits at the register cap).  The values are dropout_apply_kernel's: the same index, the same
+// f32 multiply.
+template <int EPIT, bool MASKA = false>
 __global__ __launch_bounds__(256, 2) void ffn_fused_bwd_kernel(FfnBwdArgs q) {
   const GemmArgs& p = q.e;
   extern __shared__ __attribute__((aligned(16))) float smem[];
@@ -429,6 +438,21 @@ __global__ __launch_bounds__(256, 2) void ffn_fused_bwd_kernel(FfnBwdArgs q) {
     mrow = p.out_rows ? p.out_rows[gr] : (int)gr;
     ir = ir < 0 ? 0 : ir;
     for (int j = 0; j < p.a_rowmax_n; ++j) abound = fmaxf(abound, p.a_rowmax[(int64_t)ir * p.a_rowmax_n + j]);
+    if constexpr (MASKA) {
+      abound *= p.drop_scale;                         // a bound on |dx2| in, a bound on |dy2| for the pair split
+      unsigned char* kb = reinterpret_cast<unsigned char*>(lds + FB_TAB_OFF + (q.f + GT) * 4) + ra * (GT / 8) + h;
+      // drop_keep(seed, site, base + c, thr) with the index product carried: (base + c) K = base K + c K (mod 2^32)
+      const uint32_t base = (uint32_t)(tail_token(ir, p.tail_K, p.tail_I, p.tail_pos) * GT) + 8 * h;
+      const uint32_t h0 = base * 0x9E3779B1u + p.seed, sx = q.a_site * 0x85EBCA77u;
+#pragma unroll
+      for (int kt = 0; kt < 8; ++kt) {
+        uint32_t b = 0;
+#pragma unroll
+        for (int e = 0; e < 8; ++e)
+          b |= (uint32_t)(fmix32((h0 + (uint32_t)(16 * kt + e) * 0x9E3779B1u) ^ sx) >= p.drop_thr) << e;
+        kb[2 * kt] = (unsigned char)b;
+      }
+    }
   }
   // the images' column factors (1 / s_n, NaN for an image without the pair tag), once per tile
   // (through a copy of the thread id the compiler cannot see through: it otherwise keeps 4 t, which the epilogue's
@@ -448,6 +472,16 @@ __global__ __launch_bounds__(256, 2) void ffn_fused_bwd_kernel(FfnBwdArgs q) {
   }
   int* rmeta = reinterpret_cast<int*>(lds + FF_META_OFF);
   if (h == 0) rmeta[ra] = mrow;
+  if constexpr (MASKA) {
+    // the rows' bits to memory for the W2 weight gradient (rows the map names only)
+    __syncthreads();
+    if (tt < GT) {
+      const int kr = rmeta[tt];
+      if (kr >= 0)
+        *reinterpret_cast<u32x4*>(q.keep_out + (int64_t)kr * q.ldkeep) =
+            *reinterpret_cast<const u32x4*>(lds + FB_TAB_OFF + (q.f + GT) * 4 + tt * (GT / 8));
+    }
+  }
   const float asc = pow2_scale14(abound);
   const float ainv = 1.f / asc;
   float* trw = reinterpret_cast<float*>(lds + FF_TR_OFF + wave * FF_TR_WAVE);
@@ -497,7 +531,15 @@ __global__ __launch_bounds__(256, 2) void ffn_fused_bwd_kernel(FfnBwdArgs q) {
         for (int pl = 0; pl < 2; ++pl) fb[nb][pl] = *reinterpret_cast<const u32x4*>(sb + boff + pl * 4096 + nb * 1024);
       const f32x4 a0 = *reinterpret_cast<const f32x4*>(sb + aoff0);
       const f32x4 a1 = *reinterpret_cast<const f32x4*>(sb + (aoff0 ^ 16));   // chunk 2h + 1
-      const float av[8] = {a0.x, a0.y, a0.z, a0.w, a1.x, a1.y, a1.z, a1.w};
+      float av[8] = {a0.x, a0.y, a0.z, a0.w, a1.x, a1.y, a1.z, a1.w};
+      if constexpr (MASKA) {
+        // keep ? a * scale : 0 as (a & -bit) * scale: a signed one-bit field extract and an AND per element
+        const int kb = *reinterpret_cast<const unsigned char*>(lds + FB_TAB_OFF + (q.f + GT) * 4 + ra * (GT / 8) +
+                                                               2 * kt + h);
+#pragma unroll
+        for (int e = 0; e < 8; ++e)
+          av[e] = __uint_as_float(__float_as_uint(av[e]) & (uint32_t)((kb << (31 - e)) >> 31)) * p.drop_scale;
+      }
       u32x4 fa[3];
       pair8(av, asc, fa);
 #pragma unroll
@@ -606,6 +648,19 @@ static int ffn_fused_bwd_initial() {
 }
 static std::atomic<int> g_ffn_fused_bwd{ffn_fused_bwd_initial()};
 
+// 1 (default: measured faster, profiles/r15/bwd_mask_fused.md) = where the model's block backward takes
+// ot_ffn_fused_bwd under dropout, the kernel masks dx2 itself (ot_ffn_fused_bwd_mask) and the W2 weight gradient masks
+// from its keep bits (OT_WG_D_KEEPBITS): no dropout pass, no dy2; 0 = the dropout pass; the environment variable
+// ONETRANS_BWD_MASK_FUSED (0 / 1) sets the process's initial value
+#ifndef OT_BWD_MASK_FUSED
+#define OT_BWD_MASK_FUSED 1
+#endif
+static int bwd_mask_fused_initial() {
+  const char* e = getenv("ONETRANS_BWD_MASK_FUSED");
+  return e && *e ? (atoi(e) != 0) : OT_BWD_MASK_FUSED;
+}
+static std::atomic<int> g_bwd_mask_fused{bwd_mask_fused_initial()};
+
 }  // namespace ot
 
 using namespace ot;
@@ -616,7 +671,9 @@ extern "C" int ot_ffn_fused_bwd_on(int on) {
   return old;
 }
 
-extern "C" int ot_ffn_fused_bwd(const ot_ffn_fused_bwd_args* a, void* stream) {
+// ot_ffn_fused_bwd (mask false) and ot_ffn_fused_bwd_mask
+static int ffn_fused_bwd_impl(const ot_ffn_fused_bwd_args* a, bool mask, uint32_t mask_site, uint32_t* keep_out,
+                              int64_t ldkeep, void* stream) {
   OT_REQUIRE(a, "ot_ffn_fused_bwd: null arguments");
   OT_REQUIRE(a->struct_size == sizeof(ot_ffn_fused_bwd_args),
              "ot_ffn_fused_bwd: ot_ffn_fused_bwd_args.struct_size %zu != %zu (header of another ot_version)",
@@ -645,6 +702,9 @@ extern "C" int ot_ffn_fused_bwd(const ot_ffn_fused_bwd_args* a, void* stream) {
              "ot_ffn_fused_bwd: dropout needs dx_masked (lddxm >= %d, lddxm %% 4 == 0, 16-B aligned)", GT);
   OT_REQUIRE(a->ws_bytes >= ot_mixed_gemm_rms_workspace_size(a->ntiles, GT), "ot_ffn_fused_bwd: workspace too small");
   OT_REQUIRE(!a->rowabs_out || a->rowabs_n == 1, "ot_ffn_fused_bwd: rowabs_out needs rowabs_n == 1");
+  OT_REQUIRE(!mask || (a->drop_rate > 0.f && keep_out && ldkeep >= GT / 32 && ldkeep % 4 == 0 && a16(keep_out)),
+             "ot_ffn_fused_bwd_mask: needs drop_rate > 0 and keep_out (ldkeep >= %d, ldkeep %% 4 == 0, 16-B aligned)",
+             GT / 32);
   if (a->ntiles == 0) return OT_OK;
   FfnBwdArgs q{};
   GemmArgs& p = q.e;
@@ -670,23 +730,42 @@ extern "C" int ot_ffn_fused_bwd(const ot_ffn_fused_bwd_args* a, void* stream) {
   q.img2 = a->w2_image; q.g2 = a->w2_groups > 1;
   q.img1 = a->w1_image; q.g1 = a->w1_groups > 1;
   q.u = a->u; q.ldu = a->ldu; q.du = a->du; q.lddu = a->lddu; q.du_amax = a->du_amax; q.f = a->f;
-  void (*kern)(FfnBwdArgs) = a->drop_rate > 0.f ? ffn_fused_bwd_kernel<OT_EPI_RMSNORM_BWD | OT_EPI_DROPOUT>
-                                                : ffn_fused_bwd_kernel<OT_EPI_RMSNORM_BWD>;
+  q.a_site = mask_site; q.keep_out = keep_out; q.ldkeep = ldkeep;
+  void (*kern)(FfnBwdArgs) = mask                 ? ffn_fused_bwd_kernel<OT_EPI_RMSNORM_BWD | OT_EPI_DROPOUT, true>
+                             : a->drop_rate > 0.f ? ffn_fused_bwd_kernel<OT_EPI_RMSNORM_BWD | OT_EPI_DROPOUT>
+                                                  : ffn_fused_bwd_kernel<OT_EPI_RMSNORM_BWD>;
   static std::once_flag once;                          // more than 64 KiB of LDS: opt in
   std::call_once(once, [] {
     (void)hipFuncSetAttribute((const void*)ffn_fused_bwd_kernel<OT_EPI_RMSNORM_BWD>,
                               hipFuncAttributeMaxDynamicSharedMemorySize, ffn_bwd_lds(FF_MAX_F));
     (void)hipFuncSetAttribute((const void*)ffn_fused_bwd_kernel<OT_EPI_RMSNORM_BWD | OT_EPI_DROPOUT>,
                               hipFuncAttributeMaxDynamicSharedMemorySize, ffn_bwd_lds(FF_MAX_F));
+    (void)hipFuncSetAttribute((const void*)ffn_fused_bwd_kernel<OT_EPI_RMSNORM_BWD | OT_EPI_DROPOUT, true>,
+                              hipFuncAttributeMaxDynamicSharedMemorySize, ffn_bwd_lds(FF_MAX_F, true));
     (void)hipGetLastError();
   });
   hipStream_t s = (hipStream_t)stream;
-  hipLaunchKernelGGL(kern, dim3((unsigned)a->ntiles), dim3(256), (size_t)ffn_bwd_lds(a->f), s, q);
+  hipLaunchKernelGGL(kern, dim3((unsigned)a->ntiles), dim3(256), (size_t)ffn_bwd_lds(a->f, mask), s, q);
   OT_LAUNCH_CHECK("ot_ffn_fused_bwd");
   float* dgpart = (float*)a->workspace;
   launch_colsum_reduce(dgpart, a->ntiles, GT, a->dgamma, a->accumulate_dgamma, s, dgpart + (int64_t)a->ntiles * GT);
   OT_LAUNCH_CHECK("ot_ffn_fused_bwd(dgamma)");
   return OT_OK;
+}
+
+extern "C" int ot_ffn_fused_bwd(const ot_ffn_fused_bwd_args* a, void* stream) {
+  return ffn_fused_bwd_impl(a, false, 0u, nullptr, 0, stream);
+}
+
+extern "C" int ot_ffn_fused_bwd_mask(const ot_ffn_fused_bwd_args* a, uint32_t mask_site, uint32_t* keep_out,
+                                     int64_t ldkeep, void* stream) {
+  return ffn_fused_bwd_impl(a, true, mask_site, keep_out, ldkeep, stream);
+}
+
+extern "C" int ot_bwd_mask_fused(int on) {
+  const int old = g_bwd_mask_fused.load(std::memory_order_relaxed);
+  if (on >= 0) g_bwd_mask_fused.store(on ? 1 : 0, std::memory_order_relaxed);
+  return old;
 }
 
 extern "C" int ot_ffn_fused(int on) {

@@ -60,6 +60,10 @@ struct WgradArgs {
   // TERMS 2 (the scaled fp16 pair): bounds of |A| (null with the RMSNorm prologue: sqrt(K) |gamma_k| per column)
   // and |D|, one float each (ot_mixed_gemm_wgrad_ex)
   const float* a_bound; const float* d_bound;
+  // OT_WG_D_KEEPBITS (the pair form with the GELU prologue): D is read unmasked and a row's dropout keep bits
+  // [d_row][ldkeep] (bit n % 32 of word n / 32) select D' = keep ? D * d_scale : 0; d_bound then bounds |D| and the
+  // kernel multiplies it by d_scale
+  const uint32_t* keep; int64_t ldkeep; float d_scale;
 };
 
 template <int AXT>
@@ -233,9 +237,12 @@ constexpr int wgrad_rs() { return WGRAD_BF16_RS > 0 && TERMS == 1 ? WGRAD_BF16_R
 // RMSNorm prologue's A needs none: |x_k rstd gamma_k| <= sqrt(K) |gamma_k|), the accumulator unscaled by
 // 1 / (s_k t) at the store.  Every element keeps 22 significant bits of itself down to 2^-16 of its bound (below,
 // an absolute error under 2^-38 of the bound).
-template <int AXT, int TERMS, bool DBF = false>
+// KEEP: D masked at staging time from stored keep bits (OT_WG_D_KEEPBITS) — one 16-byte word per row and stage; no
+// hashing here: every D element is read again by each of the K / 128 column-tile workgroups
+template <int AXT, int TERMS, bool DBF = false, bool KEEP = false>
 __global__ __launch_bounds__(256, 2) void wgrad_split_kernel(WgradArgs p) {
   constexpr int RS = wgrad_rs<TERMS>();
+  static_assert(!KEEP || (TERMS == 2 && AXT == OT_AX_GELU && !DBF), "keep-bits D: the pair form of the W2 gradient");
   static_assert(RS * WSPLANE <= WSOP && (TERMS == 1 || RS == 1), "wgrad stage LDS");
   static_assert(TERMS != 2 || (!DBF && (AXT == OT_AX_NONE || AXT == OT_AX_RMSNORM || AXT == OT_AX_GELU)),
                 "pair wgrad forms");
@@ -279,7 +286,7 @@ __global__ __launch_bounds__(256, 2) void wgrad_split_kernel(WgradArgs p) {
   f32x4 sa[4];
   float sdv = 1.f;
   if constexpr (PAIR) {
-    sdv = pow2_scale14(p.d_bound[0]);
+    sdv = pow2_scale14(KEEP ? p.d_bound[0] * p.d_scale : p.d_bound[0]);
     const float sqk = sqrtf((float)p.K);
     const float s1 = AXT == OT_AX_RMSNORM ? 1.f : pow2_scale14(p.a_bound[0]);
 #pragma unroll
@@ -302,6 +309,7 @@ __global__ __launch_bounds__(256, 2) void wgrad_split_kernel(WgradArgs p) {
   f32x4 va[RS][4], vd[RS][4];
   float rsd[RS];
   bool inr[RS];
+  u32x4 kw[RS];                                  // KEEP: the 128 keep bits of this thread's D row (columns n0 ..)
   auto load_stage = [&](int st, const int (&ar)[RS], const int (&dr)[RS]) {
 #pragma unroll
     for (int j = 0; j < RS; ++j) {
@@ -310,6 +318,8 @@ __global__ __launch_bounds__(256, 2) void wgrad_split_kernel(WgradArgs p) {
       const uint16_t* pa16 = reinterpret_cast<const uint16_t*>(p.A) + (int64_t)(inr[j] ? ar[j] : 0) * p.lda;
       const float* pd = p.D + (int64_t)(inr[j] ? dr[j] : 0) * p.ldd;
       rsd[j] = ax == OT_AX_RMSNORM ? p.a_rstd[inr[j] ? ar[j] : 0] : 1.f;
+      if constexpr (KEEP)
+        kw[j] = *reinterpret_cast<const u32x4*>(p.keep + (int64_t)(inr[j] ? dr[j] : 0) * p.ldkeep + (n0 >> 5));
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
         const int k = k0 + 4 * (sc + 8 * i), n = n0 + 4 * (sc + 8 * i);
@@ -350,6 +360,14 @@ __global__ __launch_bounds__(256, 2) void wgrad_split_kernel(WgradArgs p) {
         // and D must be finite — a non-finite value there (a diverged step) turns the padding rows' 0 * inf into
         // NaN in every dW tile and bias sum of a chunk with padding, where selects would have kept it to the rows
         // that hold it.  A diverged step's gradients are NaN anyway; bench.py refuses to time non-finite steps.
+        if constexpr (KEEP) {                           // float4 i holds columns 32 i + 4 sc ..: word i, nibble sc
+          // keep ? d * scale : 0 as (d & -bit) * scale
+          const int nb = (int)(kw[j][i] >> (4 * sc));
+          auto kept = [&](float v, int e) {
+            return __uint_as_float(__float_as_uint(v) & (uint32_t)((nb << (31 - e)) >> 31));
+          };
+          dv = f32x4{kept(dv.x, 0), kept(dv.y, 1), kept(dv.z, 2), kept(dv.w, 3)} * p.d_scale;
+        }
         dv = dv * (inr[j] ? 1.f : 0.f);
         bsum[i] += dv;                                  // (unconditional: cheaper than the if-converted select;
                                                         // stored only when do_bias)
@@ -1155,7 +1173,8 @@ static int wgrad_impl(const float* A, int64_t lda, const int32_t* a_rows, int a_
                       const int32_t* chunks, int nchunks, const int32_t* gchunk, int ngroups,
                       float* dW, int64_t dw_gstride, float* db, int64_t db_gstride,
                       int accumulate, void* workspace, size_t ws_bytes, const float* a_bound, const float* d_bound,
-                      int precision, void* stream) {
+                      int precision, void* stream, const uint32_t* keep = nullptr, int64_t ldkeep = 0,
+                      float d_scale = 1.f) {
   OT_REQUIRE(precision == OT_MATMUL_F32 || precision == OT_MATMUL_SPLIT_BF16 || precision == OT_MATMUL_BF16,
              "ot_mixed_gemm_wgrad: unknown precision %d", precision);
   OT_REQUIRE(A && D && dW && chunks && gchunk && workspace, "ot_mixed_gemm_wgrad: null operand");
@@ -1163,7 +1182,13 @@ static int wgrad_impl(const float* A, int64_t lda, const int32_t* a_rows, int a_
              "ot_mixed_gemm_wgrad: K, N, lda, ldd, dw_gstride must be multiples of 4");
   OT_REQUIRE(ws_bytes >= ot_wgrad_workspace_size(nchunks, K, N), "ot_mixed_gemm_wgrad: workspace too small");
   const bool dbf = (a_xform & OT_WG_D_BF16) != 0;
-  a_xform &= ~OT_WG_D_BF16;
+  const bool kbits = (a_xform & OT_WG_D_KEEPBITS) != 0;
+  a_xform &= ~(OT_WG_D_BF16 | OT_WG_D_KEEPBITS);
+  OT_REQUIRE(kbits == (keep != nullptr), "ot_mixed_gemm_wgrad: OT_WG_D_KEEPBITS goes with ot_mixed_gemm_wgrad_keep's keep");
+  OT_REQUIRE(!kbits || (precision == OT_MATMUL_SPLIT_BF16 && !dbf && a_xform == OT_AX_GELU && a_bound && d_bound &&
+                        N % GT == 0 && ldkeep >= N / 32 && ldkeep % 4 == 0 && ((uintptr_t)keep % 16) == 0),
+             "ot_mixed_gemm_wgrad: OT_WG_D_KEEPBITS needs the split mode's pair form (f32 D, OT_AX_GELU, both bounds), "
+             "N %% %d == 0, ldkeep >= N / 32, ldkeep %% 4 == 0 and 16-B aligned keep", GT);
   OT_REQUIRE(a_xform != OT_AX_RMSNORM || (a_rstd && a_gamma), "ot_mixed_gemm_wgrad: rmsnorm prologue needs rstd/gamma");
   OT_REQUIRE(!dbf || (precision == OT_MATMUL_BF16 &&
                       (a_xform == OT_AX_NONE || a_xform == OT_AX_RMSNORM || a_xform == OT_AX_BF16) &&
@@ -1175,7 +1200,7 @@ static int wgrad_impl(const float* A, int64_t lda, const int32_t* a_rows, int a_
   float* bslab = db ? slab + (size_t)nchunks * K * N : nullptr;
   if (nchunks > 0) {
     WgradArgs p{A, lda, a_rows, a_xform, a_rstd, a_gamma, D, ldd, d_rows, K, N, chunks, nchunks, slab, bslab,
-                (int)ceil_div(K, GT), (int)ceil_div(N, GT), a_bound, d_bound};
+                (int)ceil_div(K, GT), (int)ceil_div(N, GT), a_bound, d_bound, keep, ldkeep, d_scale};
     // the scaled fp16 pair: split mode, f32 operands, D's bound given, and A's (or the RMSNorm prologue's own)
     const bool pair = precision == OT_MATMUL_SPLIT_BF16 && !dbf && d_bound &&
                       ((a_xform == OT_AX_RMSNORM) || ((a_xform == OT_AX_NONE || a_xform == OT_AX_GELU) && a_bound));
@@ -1187,7 +1212,8 @@ static int wgrad_impl(const float* A, int64_t lda, const int32_t* a_rows, int a_
     const bool copy = dbf && a_xform == OT_AX_BF16 && K % 8 == 0 && N % 8 == 0 && lda % 8 == 0 &&
                       ldd % 8 == 0 && ((uintptr_t)A % 16) == 0 && ((uintptr_t)D % 16) == 0 && a_rows == d_rows;
     void (*kern)(WgradArgs) =
-        pair ? (a_xform == OT_AX_NONE      ? wgrad_split_kernel<OT_AX_NONE, 2>
+        kbits  ? wgrad_split_kernel<OT_AX_GELU, 2, false, true>
+        : pair ? (a_xform == OT_AX_NONE      ? wgrad_split_kernel<OT_AX_NONE, 2>
                 : a_xform == OT_AX_RMSNORM ? wgrad_split_kernel<OT_AX_RMSNORM, 2>
                                            : wgrad_split_kernel<OT_AX_GELU, 2>)
         : copy ? (a_rows ? wgrad_bf16_kernel<true> : wgrad_bf16_kernel<false>)
@@ -1282,4 +1308,17 @@ extern "C" int ot_mixed_gemm_wgrad_ex(const float* A, int64_t lda, const int32_t
   return wgrad_impl(A, lda, a_rows, a_xform, a_rstd, a_gamma, D, ldd, d_rows, K, N, chunks, nchunks, gchunk, ngroups,
                     dW, dw_gstride, db, db_gstride, accumulate, workspace, ws_bytes, a_bound, d_bound, precision,
                     stream);
+}
+
+extern "C" int ot_mixed_gemm_wgrad_keep(const float* A, int64_t lda, const int32_t* a_rows, int a_xform,
+                                        const float* D, int64_t ldd, const int32_t* d_rows, int K, int N,
+                                        const int32_t* chunks, int nchunks, const int32_t* gchunk, int ngroups,
+                                        float* dW, int64_t dw_gstride, float* db, int64_t db_gstride,
+                                        int accumulate, void* workspace, size_t ws_bytes, const float* a_bound,
+                                        const float* d_bound, const uint32_t* keep, int64_t ldkeep, float d_scale,
+                                        int precision, void* stream) {
+  OT_REQUIRE(keep && (a_xform & OT_WG_D_KEEPBITS), "ot_mixed_gemm_wgrad_keep: needs keep and OT_WG_D_KEEPBITS");
+  return wgrad_impl(A, lda, a_rows, a_xform, nullptr, nullptr, D, ldd, d_rows, K, N, chunks, nchunks, gchunk, ngroups,
+                    dW, dw_gstride, db, db_gstride, accumulate, workspace, ws_bytes, a_bound, d_bound, precision,
+                    stream, keep, ldkeep, d_scale);
 }

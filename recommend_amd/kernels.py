@@ -303,11 +303,14 @@ def gemm_rms(mode: int, A: Ptrish, lda: int, K: int, in_rows: Ptrish, W: Ptrish,
 def wgrad(A: Ptrish, lda: int, a_rows: Ptrish, D: Ptrish, ldd: int, d_rows: Ptrish, K: int, N: int, rmap_dev,
           nchunks: int, ngroups: int, dW: Ptrish, dw_gstride: int, db: Ptrish = None, db_gstride: int = 0, *,
           a_xform: int = 0, rstd: Ptrish = None, gamma: Ptrish = None, accumulate: bool = False,
-          device=None, m_rows: int = 0, rowmap=None, a_bound: Ptrish = None, d_bound: Ptrish = None) -> None:
+          device=None, m_rows: int = 0, rowmap=None, a_bound: Ptrish = None, d_bound: Ptrish = None,
+          keep: Ptrish = None, ldkeep: int = 0, d_scale: float = 1.0) -> None:
     """rmap_dev: dict with 'chunks'/'gchunk' device tensors; when ``rowmap`` (a layout.RowMap) is given
     its chunking is re-balanced for this call's output tile count (layout.wgrad_slots).  ``d_bound`` / ``a_bound``
     (one float each on the device, from the operands' producers): the split mode runs the fp16-pair kernel
-    (ot_mixed_gemm_wgrad_ex; the RMSNorm prologue's A needs no bound)."""
+    (ot_mixed_gemm_wgrad_ex; the RMSNorm prologue's A needs no bound).  ``keep`` (with ``a_xform`` OT_AX_GELU |
+    OT_WG_D_KEEPBITS; ot_mixed_gemm_wgrad_keep): D is the gradient before a dropout mask, masked and scaled by
+    ``d_scale`` at staging time from the rows' keep bits; ``d_bound`` then bounds the unmasked |D|."""
     if rowmap is not None and rowmap.group_rows:
         tiles = ((K + 127) // 128) * ((N + 127) // 128)
         ch, gc, nchunks = rowmap.chunks_for(tiles, device)
@@ -315,10 +318,18 @@ def wgrad(A: Ptrish, lda: int, a_rows: Ptrish, D: Ptrish, ldd: int, d_rows: Ptri
     nbytes = size('ot_wgrad_workspace_size', nchunks, K, N)
     ws = workspace(nbytes, device)
     ev = _probe.begin() if _probe is not None else None
-    call('ot_mixed_gemm_wgrad_ex', ptr(A), lda, ptr(a_rows), a_xform, ptr(rstd), ptr(gamma), ptr(D), ldd,
-         ptr(d_rows), K, N, ptr(rmap_dev['chunks']), nchunks, ptr(rmap_dev['gchunk']), ngroups, ptr(dW),
-         dw_gstride, ptr(db), db_gstride, int(accumulate), ptr(ws), ws.numel(), ptr(a_bound), ptr(d_bound), _prec(),
-         stream())
+    if keep is not None:
+        assert rstd is None and gamma is None
+        call('ot_mixed_gemm_wgrad_keep', ptr(A), lda, ptr(a_rows), a_xform, ptr(D), ldd, ptr(d_rows), K, N,
+             ptr(rmap_dev['chunks']), nchunks, ptr(rmap_dev['gchunk']), ngroups, ptr(dW), dw_gstride, ptr(db),
+             db_gstride, int(accumulate), ptr(ws), ws.numel(), ptr(a_bound), ptr(d_bound), ptr(keep), ldkeep,
+             float(d_scale), _prec(), stream())
+        a_xform &= ~_lib.OT_WG_D_KEEPBITS
+    else:
+        call('ot_mixed_gemm_wgrad_ex', ptr(A), lda, ptr(a_rows), a_xform, ptr(rstd), ptr(gamma), ptr(D), ldd,
+             ptr(d_rows), K, N, ptr(rmap_dev['chunks']), nchunks, ptr(rmap_dev['gchunk']), ngroups, ptr(dW),
+             dw_gstride, ptr(db), db_gstride, int(accumulate), ptr(ws), ws.numel(), ptr(a_bound), ptr(d_bound),
+             _prec(), stream())
     if ev is not None:
         ax = a_xform & ~_lib.OT_WG_D_BF16
         wterms = {'bf16': 1, 'f32': 0}.get(matmul_mode(), 3 if (
@@ -413,17 +424,29 @@ def ffn_fused_bwd_on(on: int = -1) -> int:
     return _lib.size('ot_ffn_fused_bwd_on', int(on))
 
 
+def bwd_mask_fused(on: int = -1) -> int:
+    """ot_bwd_mask_fused: whether the block backward, where it takes the fused FFN backward under dropout, masks dx2
+    inside that kernel and inside the W2 weight gradient (1, default: no dropout pass, no dy2) or runs the dropout pass
+    (0) —
+    or query (-1); returns the previous setting.  ``ONETRANS_BWD_MASK_FUSED`` sets the process's initial value."""
+    return _lib.size('ot_bwd_mask_fused', int(on))
+
+
 def ffn_fused_bwd(dy2: Ptrish, lddy2: int, dy2_rowmax: Ptrish, dy2_rowmax_n: int, rows: Ptrish, tile_group: Ptrish,
                   ntiles: int, w2_image, w2_groups: int, w1_image, w1_groups: int, f: int, u: Ptrish, ldu: int,
                   du: Ptrish, lddu: int, x1: Ptrish, ldx1: int, gamma: Ptrish, rstd: Ptrish, dx1: Ptrish, lddx1: int,
                   dgamma: Ptrish, *, du_amax: Ptrish = None, dres: Ptrish = None, lddres: int = 0,
                   dx_masked: Ptrish = None, lddxm: int = 0, accumulate_dgamma: bool = False, amax_out: Ptrish = None,
                   rowabs_out: Ptrish = None, rowabs_n: int = 0, seed: int = 0, site: int = 0, drop: float = 0.0,
-                  tail: Tuple[int, int] = (1, 1), m_rows: int = 0, device=None) -> None:
+                  tail: Tuple[int, int] = (1, 1), m_rows: int = 0, device=None, mask_site: Optional[int] = None,
+                  keep_out: Ptrish = None, ldkeep: int = 4) -> None:
     """ot_ffn_fused_bwd: du = (dy2 @ W2[g]^T) * gelu'(u) and dx1 = norm2_bwd(du @ W1[g]^T) + dres [, dx_masked] for
     rows of 128 floats in one launch (split mode; ``w2_image`` / ``w1_image``: the pair-form dgrad images as
     ``(tensor, element offset)``; ``dy2_rowmax``: dy2's row maxima as the FFN2 dgrad launch's ``a_rowmax``).  ``du``
-    and ``du_amax`` are bit for bit that launch's; the epilogue operands are the FFN1 dgrad launch's."""
+    and ``du_amax`` are bit for bit that launch's; the epilogue operands are the FFN1 dgrad launch's.
+    ``mask_site`` (ot_ffn_fused_bwd_mask, ``drop`` > 0): ``dy2`` is dx2, the gradient before the FFN dropout's mask at
+    that site, ``dy2_rowmax`` bounds |dx2| per row, the kernel masks at fragment time and writes the rows' keep bits
+    to ``keep_out`` [row][ldkeep] (int32 words)."""
     ws = workspace(size('ot_mixed_gemm_rms_workspace_size', ntiles, 128),
                    device if device is not None else (dx1[0] if isinstance(dx1, tuple) else dx1).device)
     a = _lib.FfnFusedBwdArgs(ctypes.sizeof(_lib.FfnFusedBwdArgs), ptr(dy2), lddy2, ptr(dy2_rowmax), int(dy2_rowmax_n),
@@ -433,7 +456,10 @@ def ffn_fused_bwd(dy2: Ptrish, lddy2: int, dy2_rowmax: Ptrish, dy2_rowmax_n: int
                              int(accumulate_dgamma), ptr(ws), ws.numel(), ptr(amax_out), ptr(rowabs_out),
                              int(rowabs_n), seed & 0xFFFFFFFF, site, float(drop), tail[0], tail[1], _sel(tail))
     ev = _probe.begin() if _probe is not None else None
-    call('ot_ffn_fused_bwd', ctypes.byref(a), stream())
+    if mask_site is not None:
+        call('ot_ffn_fused_bwd_mask', ctypes.byref(a), mask_site, ptr(keep_out), ldkeep, stream())
+    else:
+        call('ot_ffn_fused_bwd', ctypes.byref(a), stream())
     if ev is not None:
         M = m_rows or ntiles * 128
         # algorithmic bytes: dy2, u, x1, dres in; du, dx1, dx_masked out (13 R at f = 512 with dropout)
@@ -726,7 +752,7 @@ def dropout_apply(src, lds, dst, ldd, rows, d, seed, site, drop, tail, amax=None
         call(fn, ptr(src), lds, ptr(dst), ldd, rows, d, seed & 0xFFFFFFFF, site, float(drop), tail[0],
              tail[1], _sel(tail), stream())
     if ev is not None:
-        _probe.end('rowwise', 0.0, ev)
+        _probe.end('rowwise', 0.0, ev, 'dropout_apply')
 
 
 def dropout_rowmax_supported(d: int) -> bool:
@@ -739,7 +765,7 @@ def rows_absmax(x, ldx, rows, d, out) -> None:
     ev = _probe.begin() if _probe is not None else None
     call('ot_rows_absmax', ptr(x), ldx, rows, d, ptr(out), (d + 255) // 256, stream())
     if ev is not None:
-        _probe.end('rowwise', 0.0, ev)
+        _probe.end('rowwise', 0.0, ev, 'rows_absmax')
 
 
 def rows_colsum(src, ld, rows: Ptrish, nrows: int, ncols: int, out: Ptrish, accumulate=False, device=None) -> None:

@@ -204,10 +204,24 @@ class PairBounds:
     forward and its backward: a zeroed float per layer and slot, into which the producing kernel folds max |output|
     (an atomic max: the recompute's second fold of the same values changes nothing).  ``out`` is the producer's
     view; ``get`` the consumer's, None unless a producer took it — no bound, like no object: the exact split."""
-    SLOTS = ('o', 'u', 'dy2', 'du', 'dyo', 'dqkv')     # |O|, |U|, |dY2|, |dU|, |dX1 masked|, |dQKV|
+    SLOTS = ('o', 'u', 'dy2', 'du', 'dyo', 'dqkv', 'dx')   # |O|, |U|, |dY2|, |dU|, |dX1 masked|, |dQKV|, |dX|
 
     def __init__(self, layers: int, device):
         self.t, self._taken = torch.zeros(layers, 8, device=device), {}
+        self._dx = {}
+
+    def put_dx(self, l: int, dx: torch.Tensor, rowabs: torch.Tensor) -> None:
+        """Block ``l``'s input gradient with the row maxima (and, in slot 'dx', the bound) its QKV dgrad reported:
+        block ``l - 1`` masks this tensor inside its fused FFN backward (``bwd_mask_gate``)."""
+        self._dx[l] = (dx, dx._version, rowabs)
+
+    def take_dx(self, l: int, dx2: torch.Tensor):
+        """(row maxima, bound) of ``dx2`` if it is the tensor block ``l`` reported, unchanged since; else None."""
+        e = self._dx.pop(l, None)
+        if (e is None or e[0].data_ptr() != dx2.data_ptr() or e[0].shape != dx2.shape or e[1] != dx2._version
+                or not dx2.is_contiguous()):
+            return None
+        return e[2], self.get(l, 'dx')
 
     @classmethod
     def begin(cls, layers: int, device, mode: str, pair_wgrad: bool) -> Optional['PairBounds']:
@@ -228,6 +242,18 @@ def a_row_bounds(on: bool, x, ld: int, rows: int, n: int, reported=None) -> Dict
         reported = torch.empty(rows, (n + 255) // 256, device=x.device)
         K.rows_absmax(x, ld, rows, n, reported)
     return dict(a_rowmax=reported, a_rowmax_n=reported.shape[1]) if on else {}
+
+
+def bwd_mask_gate(m, l: int, rate: float, bounds, kvalid) -> bool:
+    """Does block ``l``'s backward mask dx2 inside the fused FFN backward and the W2 weight gradient (no dropout
+    pass, no dY2)?  Where ot_ffn_fused_bwd's form applies under dropout, with the pair weight gradients'
+    bounds, no padding mask, and ONETRANS_BWD_MASK_FUSED / K.bwd_mask_fused on."""
+    cfg = m.config
+    d, f = cfg.hidden_dim, cfg.ffn_dim
+    return bool(l >= 0 and rate > 0 and bounds is not None and kvalid is None and K.matmul_mode() == 'split'
+                and m.fuse_bwd and d == TILE and f % TILE == 0 and f <= K.FFN_FUSED_MAX_F
+                and m.dgrad_pair(f'blk.{l}.w2') and m.dgrad_pair(f'blk.{l}.w1')
+                and K.ffn_fused_bwd_on() and K.bwd_mask_fused())
 
 
 def _block_forward(m, l, x, I, Kq, seed, training, rstd_in=None, select=False, need_out=True, need_u=True,
@@ -524,12 +550,30 @@ class _Block(torch.autograd.Function):
         keep = (bounds.t,) if bounds is not None else ()
         # fp16-pair dgrads (pair-form dgrad images): the A rows' maxima, from the producers where they report them
         pw2, pw1, pwo = (m.dgrad_pair(f'blk.{l}.{w}') for w in ('w2', 'w1', 'wo'))
+        # split mode, d == 128, pair-form W2 / W1 dgrad images, float32 dU, the norm2 backward in the FFN1 dgrad's
+        # epilogue: both input gradients in one launch (ot_ffn_fused_bwd: dU is written for the W1 weight gradient but not
+        # read back, and its row maxima stay in registers)
+        ffn_bwd = (pw2 and pw1 and m.fuse_bwd and d == TILE and f % TILE == 0 and f <= K.FFN_FUSED_MAX_F
+                   and not du_bf and h is None and bool(K.ffn_fused_bwd_on()))
+        # ... and under dropout with the mask inside it (ot_ffn_fused_bwd_mask) and inside the W2 weight gradient
+        # (OT_WG_D_KEEPBITS, from the keep bits that kernel writes): no dropout pass, dY2 never exists.  dx2's row
+        # maxima and bound come from its producer, the QKV dgrad of the block above, else from one row-absmax pass
+        mask_fused = ffn_bwd and b_u is not None and bwd_mask_gate(m, l, rate, bounds, kvalid)
+        dx_rep = bounds.take_dx(l + 1, dx2) if bounds is not None else None
         dy2_rep = rate > 0 and not du_bf           # the float32 dropout reports |dY2|, and row maxima at some widths
-        b_dy2 = out('dy2') if dy2_rep else None
+        b_dy2 = out('dy2') if dy2_rep and not mask_fused else None
         rm_dy2 = (torch.empty(B * Kq, (d + 255) // 256, device=dev)
-                  if dy2_rep and pw2 and K.dropout_rowmax_supported(d) else None)
+                  if dy2_rep and pw2 and K.dropout_rowmax_supported(d) and not mask_fused else None)
         dy2 = dx2
-        if rate > 0:
+        if mask_fused:
+            if dx_rep is not None:
+                rm_dy2, b_dy2 = dx_rep             # (of dx2: both kernels multiply by 1 / (1 - rate))
+            else:
+                rm_dy2 = torch.empty(B * Kq, 1, device=dev)
+                K.rows_absmax(dx2, d, B * Kq, d, rm_dy2)
+                b_dy2 = rm_dy2.max().reshape(1)
+            keep_bits = torch.empty(B * Kq, d // 32, dtype=torch.int32, device=dev)
+        elif rate > 0:
             dy2 = torch.empty(B * Kq, d, device=dev, dtype=torch.int16 if du_bf else torch.float32)
             K.dropout_apply(dx2, d, dy2, d, B * Kq, d, seed, 2 * l + 1, rate, tail, amax=b_dy2, rowmax=rm_dy2)
         pa2 = a_row_bounds(pw2, dy2, d, B * Kq, d, rm_dy2)
@@ -545,7 +589,7 @@ class _Block(torch.autograd.Function):
         # (the forward's FFN1 epilogue stored it already when h is not None)
         hbf = (torch.empty(B * Kq, f, dtype=torch.int16, device=dev)
                if h is None and fused2 and K.matmul_mode() == 'bf16' else None)
-        if hbf is None:
+        if hbf is None and not mask_fused:
             with m.side(u if h is None else h, dy2, *keep):   # weight gradients overlap the dgrad chain (second stream)
                 K.wgrad(u if h is None else h, f, mt['rows'][1], dy2, d, mt['rows'][1], f, d, mt, nct, G,
                         m.g(f'blk.{l}.w2'), f * d, m.g(f'blk.{l}.b2'), d,
@@ -555,11 +599,6 @@ class _Block(torch.autograd.Function):
         # does the FFN2 dgrad report dU's bound and row maxima?  (its whole-tile vector epilogue does)
         du_rep = fused2 or (((bounds is not None and not du_bf) or pw2 or pw1) and f % TILE == 0)
         b_du = out('du') if du_rep and not du_bf else None
-        # split mode, d == 128, pair-form W2 / W1 dgrad images, float32 dU, the norm2 backward in the FFN1 dgrad's
-        # epilogue: both input gradients in one launch (ot_ffn_fused_bwd: dU is written for the W1 weight gradient but not
-        # read back, and its row maxima stay in registers)
-        ffn_bwd = (pw2 and pw1 and m.fuse_bwd and d == TILE and f % TILE == 0 and f <= K.FFN_FUSED_MAX_F
-                   and not du_bf and h is None and bool(K.ffn_fused_bwd_on()))
         rm_du = torch.empty(B * Kq, f // TILE, device=dev) if pw1 and du_rep and not ffn_bwd else None
         rep_du = dict(amax_out=b_du, rowabs_out=rm_du, rowabs_n=f // TILE if rm_du is not None else 0)
         if ffn_bwd:
@@ -574,7 +613,14 @@ class _Block(torch.autograd.Function):
                             du_amax=b_du, dres=dx2, lddres=d, dx_masked=dyo if rate > 0 else None, lddxm=d,
                             accumulate_dgamma=acc, amax_out=b_dyo, rowabs_out=rm_dyo,
                             rowabs_n=1 if rm_dyo is not None else 0, seed=seed, site=2 * l, drop=rate, tail=tail,
-                            m_rows=maps['tail'].nrows, device=dev)
+                            m_rows=maps['tail'].nrows, device=dev, mask_site=2 * l + 1 if mask_fused else None,
+                            keep_out=keep_bits if mask_fused else None, ldkeep=d // 32)
+            if mask_fused:
+                with m.side(u, dx2, keep_bits, b_dy2, *keep):   # after the launch that writes the keep bits
+                    K.wgrad(u, f, mt['rows'][1], dx2, d, mt['rows'][1], f, d, mt, nct, G, m.g(f'blk.{l}.w2'), f * d,
+                            m.g(f'blk.{l}.b2'), d, a_xform=OT_AX_GELU | _lib.OT_WG_D_KEEPBITS, accumulate=acc,
+                            device=dev, m_rows=maps['tail'].nrows, rowmap=maps['tail'], a_bound=b_u, d_bound=b_dy2,
+                            keep=keep_bits, ldkeep=d // 32, d_scale=1.0 / (1.0 - rate))
         elif fused2:
             # d > 128: the FFN2 dgrad also emits rowdot[row][f-tile] = sum dU (U - b1) for the norm2 backward
             rowdot = torch.empty(B * Kq, f // TILE, device=dev)
@@ -672,13 +718,20 @@ class _Block(torch.autograd.Function):
                     rowmap=maps['all'], d_bound=b_dq)
         ax_dq = OT_AX_BF16 if dq_bf else 0
         dx = torch.empty(B * I, d, device=dev)
+        # the block below masks dx inside its fused FFN backward: this launch reports dx's row maxima and bound
+        rep_dx = {}
+        if pqkv and bwd_mask_gate(m, l - 1, rate, bounds, None):
+            rm_dx = torch.empty(B * I, 1, device=dev)
+            rep_dx = dict(amax_out=out('dx'), rowabs_out=rm_dx, rowabs_n=1)
         if m.fuse_bwd:         # QKV dgrad -> norm1 backward + residual (dx1 on the kept tail rows)
             K.gemm_rms(OT_GEMM_NT, dqkv, 3 * d, 3 * d, ma['rows'][0], m.p(f'blk.{l}.wqkv'), 3 * d * d, 3 * d, d,
                        ma['tile_group'], na, dx, d, ma['rows'][0], epi=OT_EPI_RMSNORM_BWD, a_xform=ax_dq,
                        m_rows=maps['all'].nrows, nx=x, ldnx=d, ngamma=m.p(f'blk.{l}.norm1'), nrstd=rstd1,
                        dres=dx1, lddres=d, dres_tail=(Kq, I, inv) if Kq < I else (0, 0),
                        dgamma=m.g(f'blk.{l}.norm1'), accumulate_dgamma=acc, device=dev,
-                       bimg=m.bimg(f'blk.{l}.wqkv', 'dgrad'), **pa_q)
+                       bimg=m.bimg(f'blk.{l}.wqkv', 'dgrad'), **pa_q, **rep_dx)
+            if rep_dx:
+                bounds.put_dx(l, dx, rm_dx)
         else:
             dxn1 = torch.empty(B * I, d, device=dev)
             K.gemm_rms(OT_GEMM_NT, dqkv, 3 * d, 3 * d, ma['rows'][0], m.p(f'blk.{l}.wqkv'), 3 * d * d, 3 * d, d,

@@ -3,20 +3,25 @@ backward (FFN2 dgrad: GELU' epilogue, dU's row maxima and max |dU|; FFN1 dgrad: 
 dropout mask, dgamma) and as the fused kernel (ot_ffn_fused_bwd).
 HIP events, interleaved rounds, min / median per variant; dU is compared bit for bit and dx1 / dyo within the
 plane-vs-staged tolerance.  `--once VARIANT` runs one variant three times (for a trace or PMC pass of its own).
+`--mask-fused` times the FFN dropout's backward instead: {dropout pass + fused backward + W2 weight gradient} against
+{fused backward masking dx2 itself (ot_ffn_fused_bwd_mask) + W2 weight gradient from its keep bits}, one stream, every
+output compared bit for bit.
 Iteration tool; never part of the product path."""
 import argparse, math, os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np, torch
 from recommend_amd import kernels as K
-from recommend_amd._lib import OT_EPI_DROPOUT, OT_EPI_GELU_BWD, OT_EPI_RMSNORM_BWD, OT_GEMM_NT
-from recommend_amd.layout import IMAGE_UNIT_ELEMS
+from recommend_amd._lib import (OT_AX_GELU, OT_EPI_DROPOUT, OT_EPI_GELU_BWD, OT_EPI_RMSNORM_BWD, OT_GEMM_NT,
+                                OT_WG_D_KEEPBITS)
+from recommend_amd.layout import IMAGE_UNIT_ELEMS, identity_map
 
 ap = argparse.ArgumentParser()
 ap.add_argument('--rounds', type=int, default=15)
 ap.add_argument('--batch', type=int, default=4096)
 ap.add_argument('--ffn', type=int, default=512)
 ap.add_argument('--drop', type=float, default=0.1)
-ap.add_argument('--once', default=None, help='run one variant only (two, fused): profiling passes')
+ap.add_argument('--once', default=None, help='run one variant only (two, fused; pass, mask): profiling passes')
+ap.add_argument('--mask-fused', action='store_true', help='the dropout pass against the in-kernel mask (drop > 0)')
 args = ap.parse_args()
 
 dev = torch.device('cuda')
@@ -79,6 +84,44 @@ def fused():
 
 
 variants = {'two': two, 'fused': fused}
+if args.mask_fused:
+    assert args.drop > 0
+    imap = identity_map(M)
+    cmap, nch = imap.to(dev), imap.chunks.shape[0]
+    scale = float(np.float32(1) / (np.float32(1) - np.float32(args.drop)))
+    dy2m, rm_m, b_m = torch.empty(M, d, device=dev), torch.empty(M, 1, device=dev), torch.zeros(1, device=dev)
+    rm_x = torch.empty(M, 1, device=dev)
+    K.rows_absmax(dx2, d, M, d, rm_x)                                # (the model: reported by dx2's producer)
+    b_x, b_u = dx2.abs().max().reshape(1), u.abs().max().reshape(1)
+    keep = torch.empty(M, d // 32, dtype=torch.int32, device=dev)
+    dW2, db2 = torch.empty(1, f, d, device=dev), torch.empty(1, d, device=dev)
+    wkw = dict(device=dev, a_bound=b_u, m_rows=M, rowmap=imap)
+
+    def fused_on(a, rm, **kw):
+        K.ffn_fused_bwd(a, d, rm, 1, rows, tg, ntiles, im2, 1, im1, 1, f, u, f, du, f, x1, d, gamma, rstd, dx1, d, dg,
+                        du_amax=b_du, dres=dx2, lddres=d, dx_masked=dxm, lddxm=d, amax_out=b_dyo, rowabs_out=rm_dyo,
+                        rowabs_n=1, seed=7, site=0, drop=args.drop, tail=tail, device=dev, **kw)
+
+    def with_pass():
+        K.dropout_apply(dx2, d, dy2m, d, M, d, 7, 1, args.drop, tail, amax=b_m, rowmax=rm_m)
+        fused_on(dy2m, rm_m)
+        K.wgrad(u, f, rows, dy2m, d, rows, f, d, cmap, nch, 1, dW2, f * d, db2, d, a_xform=OT_AX_GELU, d_bound=b_m, **wkw)
+
+    def with_mask():
+        fused_on(dx2, rm_x, mask_site=1, keep_out=keep, ldkeep=d // 32)
+        K.wgrad(u, f, rows, dx2, d, rows, f, d, cmap, nch, 1, dW2, f * d, db2, d, a_xform=OT_AX_GELU | OT_WG_D_KEEPBITS,
+                d_bound=b_x, keep=keep, ldkeep=d // 32, d_scale=scale, **wkw)
+
+    variants = {'pass': with_pass, 'mask': with_mask}
+    outs = lambda: [t.clone() for t in (du, dx1, dyo, dW2, db2)]
+    with_pass(); torch.cuda.synchronize(); ref_m = outs()
+    with_mask(); torch.cuda.synchronize()
+    # the same binade of scale x bound in both paths wherever max |dx2| x scale rounds like max |dy2| (the kept
+    # maximum): then every bit agrees; a row whose maximum was dropped has a finer scale in the pass path
+    same = [torch.equal(a.view(torch.int32), b.view(torch.int32)) for a, b in zip(outs(), ref_m)]
+    print('bitwise equal to the pass path (du, dx1, dyo, dW2, db2):', same)
+    for a, b in zip(outs(), ref_m):
+        torch.testing.assert_close(a, b, rtol=2e-5, atol=2e-5 * math.sqrt(f))
 if args.once:
     variants = {args.once: variants[args.once]}
 ref = None
@@ -86,6 +129,8 @@ for v, fn in variants.items():                                       # warm-up +
     du.fill_(float('nan')); dx1.fill_(float('nan')); dyo.fill_(float('nan'))
     fn(); fn(); fn()
     torch.cuda.synchronize()
+    if args.mask_fused:
+        continue                                                     # (compared above)
     if ref is None:
         ref = (du.clone(), dx1.clone(), dyo.clone())
     else:
