@@ -1010,6 +1010,15 @@ int ot_ns_group_bwd_weight(const float* A, int64_t lda, const float* D, int64_t 
                            int ktot, int kmax, int B, int d, float* dW, float* db, int accumulate, void* workspace,
                            size_t ws_bytes, void* stream);
 
+/* ---- probe of the scaled fp16-pair split (pair_probe.hip; a test hook, on no hot path) -------------------
+ * The two fp16 planes (bit patterns) the pair GEMMs form from an f32 operand: with t = f32(x[i] * scale),
+ *   form 0 (the plane GEMMs' and the fused FFN's split): t saturated to [-65504, 65504] (a NaN stays a NaN),
+ *   form 1 (the pair weight gradient's split) and form 2 (the slice attention's split): t as it is,
+ * hi[i] = fp16(t), lo[i] = fp16(t - f32(hi[i])), both rounded to nearest even.  n is a multiple of 8 (form 0) or
+ * 4 (forms 1, 2); x, hi, lo are 16-byte aligned device pointers.  Stream-ordered, no allocation. */
+int ot_pair_split_probe(const float* x, int64_t n, float scale, int form, uint16_t* hi, uint16_t* lo,
+                        void* stream);
+
 #ifdef __cplusplus
 }
 #endif

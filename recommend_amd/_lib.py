@@ -250,6 +250,7 @@ SIGNATURES = {
     'ot_ns_group_wgrad_workspace_size': (c_size_t, [c_int, c_int, c_int, c_int]),
     'ot_ns_group_bwd_weight': (c_int, [P, I64, P, I64, P, c_int, c_int, c_int, c_int, c_int, P, P, c_int, P,
                                        c_size_t, P]),
+    'ot_pair_split_probe': (c_int, [P, I64, c_float, c_int, P, P, P]),
 }
 
 # ABI notes (mirrors include/onetrans_hip.h): the modes/flags above; the device-side struct is

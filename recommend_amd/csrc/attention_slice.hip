@@ -105,8 +105,10 @@ __device__ __forceinline__ void tr_at(u32x4 (&f)[3], const char* p0, const char*
     f[pl] = u32x4{x.x, x.y, y.x, y.y};
   }
 }
-// split8 with the two subtractions of each element pair on packed-f32 adds (v_pk_add_f32); the planes are
-// the high halves of x, r1, r2 (v_perm), so only the residuals need the masked values.  Bit-identical to split8.
+// split8 with the two subtractions of each element pair written on a two-element vector (this file is built without
+// packed f32, Makefile SCALAR_F32_SRCS: two v_sub_f32, cheaper beside MFMAs than one v_pk_add_f32,
+// profiles/r16/valu_issue.md); the planes are the high halves of x, r1, r2 (v_perm), so only the residuals need the
+// masked values.  Bit-identical to split8.
 __device__ __forceinline__ void split8p(const float* v, u32x4 (&pl)[3]) {
   typedef float f32x2 __attribute__((ext_vector_type(2)));
   uint32_t a[4], b[4], c[4];
@@ -190,7 +192,7 @@ __device__ __forceinline__ void splitN(const float* v, float s, u32x4 (&pl)[NP])
     for (int k = 0; k < 4; ++k) {
       const f32x2 x = f32x2{v[2 * k], v[2 * k + 1]} * s;
       const f16x2 h = __builtin_convertvector(x, f16x2);
-      const f16x2 l = __builtin_convertvector(x - __builtin_convertvector(h, f32x2), f16x2);
+      const f16x2 l = ot::pair_lo_mix(x, h);
       a[k] = __builtin_bit_cast(uint32_t, h);
       b[k] = __builtin_bit_cast(uint32_t, l);
     }

@@ -21,8 +21,10 @@ namespace ot {
 // f32x4 -> three planes of 4 bf16 (each packed into 2 dwords, element 0 in the low half):
 // x = x0 + x1 + x2 exactly (x0 the top 8 significant bits, x1 the next 8, x2 the rest; truncation
 // keeps every step exact)
-// The subtractions run on packed-f32 adds (v_pk_add_f32, two elements each) and the planes are the high halves
-// of x, r1, r2 (v_perm): the masked values are needed only as the subtrahends.
+// The subtractions are written on two-element vectors and the planes are the high halves of x, r1, r2 (v_perm): the
+// masked values are needed only as the subtrahends.  A file built with packed f32 runs them as v_pk_add_f32, a file of
+// Makefile SCALAR_F32_SRCS as two v_sub_f32, which is the cheaper form beside MFMAs: one packed f32 op in an MFMA gap
+// measured ~18 cycles against ~1 for its two scalar halves (profiles/r16/valu_issue.md).
 __device__ __forceinline__ void split3(f32x4 v, u32x2& p0, u32x2& p1, u32x2& p2) {
   typedef float f32x2_ __attribute__((ext_vector_type(2)));
   uint32_t a[4], b[4], c[4];
@@ -112,12 +114,29 @@ __device__ __forceinline__ float pow2_scale14(float m) {
   // an inf / NaN bound (a diverged producer) gives a NaN scale: the product turns NaN instead of silently 0
   return e == 255 ? __builtin_nanf("") : __uint_as_float((uint32_t)se << 23);
 }
+// the residual plane of one element pair: l = fp16(x - f32(h)) per half, h = the packed fp16(x).  x - f32(h) is exact
+// in f32, so every form below gives the same bits.  pair_lo leaves the form to the compiler: with packed f32 two
+// v_cvt_f32_f16 + v_pk_add_f32 + v_cvt_pk_f16_f32, without it two v_sub_f32 (or v_fma_mix_f32 where the scale's
+// multiply contracts into it).  pair_lo_mix reads h's halves in place and rounds x * 1 - h once to fp16
+// (v_fma_mixlo_f16 + v_fma_mixhi_f16, no convert): beside MFMAs it prices like 2 v_fma_mix_f32 + v_cvt_pk_f16_f32
+// (profiles/r16/valu_issue.md), and it is used where a kernel measured faster with it (the slice attention's split,
+// profiles/r16/valu_depack.md; in pair8 it measured no gain and in pair4 a loss).
+__device__ __forceinline__ f16x2_t pair_lo(f32x2_t x, f16x2_t h) {
+  return __builtin_convertvector(x - __builtin_convertvector(h, f32x2_t), f16x2_t);
+}
+__device__ __forceinline__ f16x2_t pair_lo_mix(f32x2_t x, f16x2_t h) {
+  uint32_t l;   // the low half first; early clobber: the second instruction still reads x and h
+  asm("v_fma_mixlo_f16 %0, %1, 1.0, -%3 op_sel_hi:[0,0,1]\n\t"
+      "v_fma_mixhi_f16 %0, %2, 1.0, -%3 op_sel:[0,0,1] op_sel_hi:[0,0,1]"
+      : "=&v"(l)
+      : "v"(x.x), "v"(x.y), "v"(__builtin_bit_cast(uint32_t, h)));
+  return __builtin_bit_cast(f16x2_t, l);
+}
 // 4 floats (already scaled) -> the fp16 pair's planes, 8 B each
 __device__ __forceinline__ void pair4(f32x4 v, u32x2& hi, u32x2& lo) {
   const f32x2_t x0 = f32x2_t{v.x, v.y}, x1 = f32x2_t{v.z, v.w};
   const f16x2_t h0 = __builtin_convertvector(x0, f16x2_t), h1 = __builtin_convertvector(x1, f16x2_t);
-  const f16x2_t l0 = __builtin_convertvector(x0 - __builtin_convertvector(h0, f32x2_t), f16x2_t);
-  const f16x2_t l1 = __builtin_convertvector(x1 - __builtin_convertvector(h1, f32x2_t), f16x2_t);
+  const f16x2_t l0 = pair_lo(x0, h0), l1 = pair_lo(x1, h1);
   hi = u32x2{__builtin_bit_cast(uint32_t, h0), __builtin_bit_cast(uint32_t, h1)};
   lo = u32x2{__builtin_bit_cast(uint32_t, l0), __builtin_bit_cast(uint32_t, l1)};
 }
@@ -137,16 +156,20 @@ __device__ __forceinline__ void amax_flush(float* amax, float m) {
   if (amax && (threadIdx.x & 63) == 0 && __float_as_uint(m) > *reinterpret_cast<volatile unsigned int*>(amax))
     atomicMax(reinterpret_cast<unsigned int*>(amax), __float_as_uint(m));
 }
-// x s is saturated to the fp16 range first (v_med3_f32): a row bound that under-estimates the operand (a stale or
-// wrong a_rowmax) then gives a deterministic, finite, clipped product instead of an inf plane and inf - inf = NaN
+// x s is saturated to the fp16 range first: a row bound that under-estimates the operand (a stale or wrong a_rowmax)
+// then gives a deterministic, finite, clipped product instead of an inf plane and inf - inf = NaN.  The saturation is
+// v_maximum3_f32 + v_minimum3_f32, which hand a NaN on (a NaN operand or a NaN scale, pow2_scale14, turns the
+// product NaN); v_med3_f32, one instruction less, returned -65504 for a NaN (tests/test_pair_split_gpu.py).
+__device__ __forceinline__ float sat_f16(float x) {
+  return __builtin_elementwise_minimum(__builtin_elementwise_maximum(x, -65504.f), 65504.f);
+}
 __device__ __forceinline__ void pair8(const float* v, float s, u32x4 (&pl)[3]) {
   uint32_t a[4], b[4];
 #pragma unroll
   for (int k = 0; k < 4; ++k) {
-    const f32x2_t x = f32x2_t{__builtin_amdgcn_fmed3f(v[2 * k] * s, -65504.f, 65504.f),
-                              __builtin_amdgcn_fmed3f(v[2 * k + 1] * s, -65504.f, 65504.f)};
+    const f32x2_t x = f32x2_t{sat_f16(v[2 * k] * s), sat_f16(v[2 * k + 1] * s)};
     const f16x2_t h = __builtin_convertvector(x, f16x2_t);
-    const f16x2_t l = __builtin_convertvector(x - __builtin_convertvector(h, f32x2_t), f16x2_t);
+    const f16x2_t l = pair_lo(x, h);
     a[k] = __builtin_bit_cast(uint32_t, h);
     b[k] = __builtin_bit_cast(uint32_t, l);
   }
@@ -215,9 +238,12 @@ __device__ __forceinline__ int64_t kept_row(int64_t o, int K, int I, const int32
 // fp32).  This is the float erf TensorFlow's CPU kernels evaluate (Eigen's generic fast erf), so it
 // is also the reference's own arithmetic; ~15 VALU ops instead of the two-regime libm erff.
 // Every multiply-add is an explicit fma (no contraction left to the compiler) so the scalar form and the
-// packed-pair form below give identical bits per element; the pair form runs the polynomials on
-// v_pk_fma_f32 / v_pk_mul_f32 (half the VALU issue of four scalar evaluations: the GELU prologues and
-// epilogues of the FFN GEMMs evaluate it once per element of a [rows, f] tensor).
+// two-element form below give identical bits per element.  The two-element form compiles to v_pk_fma_f32 /
+// v_pk_mul_f32 only in a file built with packed f32: half the instructions, not half the issue.  Measured
+// (profiles/r16/valu_issue.md): with no MFMA on the SIMD 3 packed ops take 18-19.5 cycles against 30-31.5 for 6
+// scalar ones, but one packed op in an MFMA gap costs ~18 cycles where its two scalar halves cost ~1.  Which wins is
+// measured per file (Makefile SCALAR_F32_SRCS, profiles/r16/valu_depack.md): the GELU-prologue weight gradient runs
+// this source faster as scalar v_fma_f32 / v_mul_f32, the fused FFN and the plane GEMMs faster packed.
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 #define OT_ERF_P(V, T)                                                   \
   V = __builtin_elementwise_fma(V, x2, (T)(2.77068142495902e-08f));      \

@@ -356,7 +356,7 @@ __global__ __launch_bounds__(256, 2) void wgrad_split_kernel(WgradArgs p) {
         }
         // only D is zeroed, for rows past the chunk or with a negative id: their A (row 0 of the map, clamped
         // columns) is finite, so its products are 0; columns past K / N feed outputs that are never stored
-        // (a 0 / 1 row factor: two packed multiplies instead of four selects).  Finiteness assumption: row 0 of A
+        // (a 0 / 1 row factor: four multiplies, no compare-and-select chain).  Finiteness assumption: row 0 of A
         // and D must be finite — a non-finite value there (a diverged step) turns the padding rows' 0 * inf into
         // NaN in every dW tile and bias sum of a chunk with padding, where selects would have kept it to the rows
         // that hold it.  A diverged step's gradients are NaN anyway; bench.py refuses to time non-finite steps.

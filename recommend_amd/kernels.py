@@ -768,6 +768,17 @@ def rows_absmax(x, ldx, rows, d, out) -> None:
         _probe.end('rowwise', 0.0, ev, 'rows_absmax')
 
 
+def pair_split_probe(x: torch.Tensor, scale: float, form: str = 'pair8'):
+    """ot_pair_split_probe: the (hi, lo) fp16 planes, as int16 bit patterns, that the pair GEMMs form from the flat
+    f32 tensor ``x`` at ``scale``; ``form`` 'pair8' (saturating; numel a multiple of 8), 'pair4' (the weight gradient's)
+    or 'slice' (the slice attention's; both: numel a multiple of 4)."""
+    hi = torch.empty(x.numel(), dtype=torch.int16, device=x.device)
+    lo = torch.empty_like(hi)
+    call('ot_pair_split_probe', ptr(x), x.numel(), float(scale), {'pair8': 0, 'pair4': 1, 'slice': 2}[form], ptr(hi), ptr(lo),
+         stream())
+    return hi, lo
+
+
 def rows_colsum(src, ld, rows: Ptrish, nrows: int, ncols: int, out: Ptrish, accumulate=False, device=None) -> None:
     ws = workspace(size('ot_rows_colsum_workspace_size', nrows, ncols), device)
     ev = _probe.begin() if _probe is not None else None
