@@ -395,7 +395,7 @@ int ot_ffn_fused_bwd_mask(const ot_ffn_fused_bwd_args* args, uint32_t mask_site,
  * returns the previous setting.  The library only keeps the setting: the host layer reads it. */
 int ot_bwd_mask_fused(int on);
 
-/* ---- causal attention with a query tail (attention.hip) ----------------------------------
+/* ---- causal attention with a query tail (attention.hip; kernels: attn.h lists the files) --
  * Replaces model.py:100-114 (einsum QK^T/sqrt(hd), band_part mask with -1e9, softmax, einsum PV)
  * and the pyramid gather of queries model.py:356/371 (only the last K of I queries computed).
  * qkv: [B*I, ld] (q | k | v, head h at +h*head_dim); out: [B*K, H*head_dim]; lse: [B, H, K].

@@ -5,75 +5,18 @@
 // head) wave of stage II reads.  Rounding happens only when a row is stored:
 //   ot_kv_pack_bf16          K | V columns of a span's f32 qkv rows -> the request's bf16 rows (one pass, in place
 //                            at row0: the append of extend_requests writes behind the rows already there)
-//   ot_attn_fwd_cached_kv16  attn_fwd_cached_kernel (attention.hip) with the cached keys read as bf16 and widened
+//   ot_attn_fwd_cached_kv16  attn_fwd_cached_kernel (attention_wave.hip) with the cached keys read as bf16 and widened
 //                            in registers (bf16 -> f32 is a 16-bit shift, exact); a candidate's own rows stay f32,
 //                            and the arithmetic is the f32 MFMA of the f32 kernel, so the result is the exact
 //                            attention over [rounded cache ; f32 own rows] to f32 summation order.
-// The fragment helpers are attention.hip's (same lane maps), repeated here so that translation unit — and with it
-// the fp32 serving path's code — stays as it is.
-#include "common.h"
+// The f32 fragment helpers (acc_row, mm_frag, frag_to_lds, acc_tile_p, load_row_frag) are attn.h's, shared with the
+// f32 kernels; only the bf16 row load is this file's.
+#include "attn.h"
 
 namespace ot {
 namespace kv16 {
 
-__device__ __forceinline__ int acc_row(int r, int hh) { return (r & 3) + 8 * (r >> 2) + 4 * hh; }
-
-constexpr int NB(int hd) { return (hd + 31) / 32; }
-
-template <int HD>
-constexpr int TLD() { return HD + 4; }
-
-template <int HD>
-__device__ __forceinline__ f32x16 mm_frag(const float (&a)[HD / 2], const float (&b)[HD / 2]) {
-  f32x16 acc;
-#pragma unroll
-  for (int r = 0; r < 16; ++r) acc[r] = 0.f;
-#pragma unroll
-  for (int s = 0; s < HD / 2; ++s) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a[s], b[s], acc, 0, 0, 0);
-  return acc;
-}
-
-template <int HD>
-__device__ __forceinline__ void frag_to_lds(float* tile, const float (&f)[HD / 2], int li, int hh) {
-#pragma unroll
-  for (int q = 0; q < HD / 8; ++q)
-    *reinterpret_cast<f32x4*>(tile + li * TLD<HD>() + (HD / 2) * hh + 4 * q) =
-        f32x4{f[4 * q], f[4 * q + 1], f[4 * q + 2], f[4 * q + 3]};
-}
-
-// acc[c] (+)= sum_r tile[row(r)][32c + li] * p[r]
-template <int HD>
-__device__ __forceinline__ void acc_tile_p(f32x16 (&acc)[NB(HD)], const float* tile, const f32x16& p, int li,
-                                           int hh) {
-#pragma unroll
-  for (int r = 0; r < 16; ++r) {
-    const int row = acc_row(r, hh);
-#pragma unroll
-    for (int c = 0; c < NB(HD); ++c) {
-      const int dd = 32 * c + li;
-      const float a = dd < HD ? tile[row * TLD<HD>() + dd] : 0.f;
-      acc[c] = __builtin_amdgcn_mfma_f32_32x32x2f32(a, p[r], acc[c], 0, 0, 0);
-    }
-  }
-}
-
-// lane (li, hh): dims (HD/2)*hh + s of an f32 row (null: zeros)
-template <int HD>
-__device__ __forceinline__ void load_row_frag(float (&f)[HD / 2], const float* row, int hh) {
-  if (row) {
-    const float* q = row + (HD / 2) * hh;
-#pragma unroll
-    for (int i = 0; i < HD / 8; ++i) {
-      const f32x4 v = *reinterpret_cast<const f32x4*>(q + 4 * i);
-      f[4 * i] = v.x; f[4 * i + 1] = v.y; f[4 * i + 2] = v.z; f[4 * i + 3] = v.w;
-    }
-  } else {
-#pragma unroll
-    for (int s = 0; s < HD / 2; ++s) f[s] = 0.f;
-  }
-}
-
-// the same dims of a bf16 row: HD bytes as HD/16 16-byte loads, widened (element 2i the low half of dword i)
+// load_row_frag's dims of a bf16 row: HD bytes as HD/16 16-byte loads, widened (element 2i the low half of dword i)
 template <int HD>
 __device__ __forceinline__ void load_row_frag16(float (&f)[HD / 2], const uint16_t* row, int hh) {
   const uint16_t* q = row + (HD / 2) * hh;

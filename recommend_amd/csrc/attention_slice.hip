@@ -3,7 +3,7 @@
 // gradient for the f32-accurate mode (OT_MATMUL_SPLIT_BF16) at head_dim 32 / 64; the backward also in two long
 // forms at head_dim 64 (I <= 544, K <= 272: the query side in LDS, the key side from global; see bwd_form).
 //
-// Why a new kernel family: the per-(sample, head)-wave kernels of attention.hip
+// Why a new kernel family: the per-(sample, head)-wave kernels of attention_wave.hip
 // walk (key block, query block) pairs and re-read the Q / dO block and read-modify-write the running
 // dQ partial once per pair (about 2x the compulsory bytes through L2 at I = 140), on f32 MFMA
 // (64 cycles per 32x32x2).  Here one workgroup owns a whole (sample, head) slice:

@@ -19,6 +19,13 @@ from oracle import keras_math as km
 TOL = dict(rtol=2e-5, atol=2e-5)
 
 
+def both_modes(cases):
+    """Parameters (matmul, *case) for the `matmul` fixture (indirect): every case in 'split' mode, the default, under
+    the id it has always had (the bare case), and in 'f32' mode under 'f32-<case>'."""
+    return [pytest.param(mode, *c, id=('' if mode == 'split' else 'f32-') + '-'.join(map(str, c)))
+            for c in cases for mode in ('split', 'f32')]
+
+
 def gelu64(x):
     return 0.5 * x * (1.0 + torch.erf(x / math.sqrt(2.0)))
 
@@ -233,19 +240,28 @@ def attn_ref(qkv, B, H, I, Kq, hd):
     return torch.einsum('bhqk,bkhd->bqhd', torch.softmax(s, -1), v).reshape(B * Kq, d)
 
 
-@pytest.mark.parametrize('B,H,I,Kq,hd', [(3, 4, 140, 140, 32), (2, 4, 140, 1, 32), (2, 2, 70, 33, 64),
+@pytest.mark.parametrize('matmul,B,H,I,Kq,hd', both_modes([(3, 4, 140, 140, 32), (2, 4, 140, 1, 32), (2, 2, 70, 33, 64),
                                          (3, 4, 40, 40, 16), (1, 2, 33, 17, 128), (2, 4, 5, 5, 32),
                                          # short tails (VALU backward): K <= 4
                                          (2, 4, 140, 3, 32), (2, 2, 70, 4, 64), (2, 2, 33, 2, 128),
                                          (3, 4, 40, 1, 16), (2, 4, 5, 5 - 1, 32),
-                                         # shared-K/V forward (>= 3 query blocks, K/V fit in LDS)
+                                         # shared-K/V forward in 'f32' mode (>= 3 query blocks, K/V fit in LDS:
+                                         # I <= 128 at head_dim 64, so (2, 2, 150, 150, 64) is the one-wave forward)
                                          (2, 4, 100, 96, 32), (2, 2, 150, 150, 64), (3, 4, 130, 70, 16),
-                                         # split-bf16 forward (I > 256, K/V beyond the shared-K/V LDS)
+                                         (1, 2, 100, 96, 64),
+                                         # split-bf16 forward in 'split' mode (I > 256, K/V beyond the shared-K/V LDS)
                                          (2, 4, 300, 300, 32), (1, 2, 300, 137, 64), (1, 2, 290, 100, 128),
                                          # hd 32 tail backward with in-kernel row statistics up to K = 160
-                                         # (attn_bwd_kernel FDL), and the prep-kernel form just past it
-                                         (2, 4, 170, 160, 32), (1, 4, 170, 161, 32)])
-def test_attention(dev, B, H, I, Kq, hd):
+                                         # (attn_bwd_kernel FDL, 'f32' mode), and the prep-kernel form just past it
+                                         (2, 4, 170, 160, 32), (1, 4, 170, 161, 32),
+                                         # one query at head_dim 64 and 128 (the short-tail kernels' KQ = 1 instances)
+                                         (1, 2, 33, 1, 64), (1, 1, 33, 1, 128),
+                                         # head_dim 16 with 2 .. 4 queries: the one-wave forward, the short-tail backward
+                                         (1, 2, 33, 3, 16)]), indirect=['matmul'])
+def test_attention(dev, matmul, B, H, I, Kq, hd):
+    """Both f32-accurate modes: 'split' takes the slice kernels wherever they fit (head_dim 32 up to I = 192, head_dim
+    64 up to I = 144) and the split-plane forward past I = 256; 'f32' reaches the shared-K/V forward and the
+    one-wave-per-(sample, head) kernels at every shape."""
     torch.manual_seed(0)
     d = H * hd
     qkv = torch.randn(B * I, 3 * d, dtype=torch.float64)
@@ -279,8 +295,8 @@ def attn_ref_sel(qkv, B, H, I, qpos, hd):
     return torch.einsum('bhqk,bkhd->bqhd', torch.softmax(s, -1), v).reshape(B * Kq, d)
 
 
-@pytest.mark.parametrize('hd', [16, 32])
-def test_attention_fwd_spread_block_queries(dev, hd):
+@pytest.mark.parametrize('matmul,hd', both_modes([(16,), (32,)]), indirect=['matmul'])
+def test_attention_fwd_spread_block_queries(dev, matmul, hd):
     """Shared-K/V forward with the kept queries of one query block spread over the sequence (40 .. 139:
     its early queries see none of the later key blocks, which stay fully masked for them); the
     output and the log-sum-exp against float64."""
@@ -305,10 +321,11 @@ def test_attention_fwd_spread_block_queries(dev, hd):
     torch.testing.assert_close(lse.double().cpu().reshape(B, H, Kq), ref_lse, rtol=1e-5, atol=1e-5)
 
 
-@pytest.mark.parametrize('B,H,I,Kq,hd', [(3, 4, 140, 70, 32), (2, 2, 70, 33, 64), (3, 4, 40, 12, 16),
+@pytest.mark.parametrize('matmul,B,H,I,Kq,hd', both_modes([(3, 4, 140, 70, 32), (2, 2, 70, 33, 64), (3, 4, 40, 12, 16),
                                          (1, 2, 33, 17, 128), (2, 4, 140, 3, 32), (2, 2, 70, 4, 64),
-                                         (2, 4, 150, 100, 32), (2, 2, 524, 262, 64), (2, 4, 9, 9, 32)])
-def test_attention_selected_queries(dev, B, H, I, Kq, hd):
+                                         (2, 4, 150, 100, 32), (2, 2, 524, 262, 64), (2, 4, 9, 9, 32)]),
+                         indirect=['matmul'])
+def test_attention_selected_queries(dev, matmul, B, H, I, Kq, hd):
     """Queries at per-sample kept positions (ot_pyramid_select's output), every kernel variant:
     one-wave and shared-K/V forwards, MFMA and short-tail (K <= 4) backwards."""
     rng = np.random.default_rng(I * 7 + Kq)
@@ -653,7 +670,9 @@ def test_bf16_mode_bounds(dev):
 @pytest.mark.parametrize('mode', ['split', 'bf16'])
 @pytest.mark.parametrize('B,H,I,Kq,hd,sel', [(2, 4, 140, 140, 32, False), (2, 4, 140, 70, 32, True),
                                              (2, 2, 150, 150, 64, False), (2, 2, 300, 120, 64, True),
-                                             (3, 4, 40, 12, 32, False)])
+                                             (3, 4, 40, 12, 32, False),
+                                             # head_dim 128: in bf16 mode the one-plane forward, the f32 backward
+                                             (1, 2, 33, 17, 128, False)])
 def test_attention_backward_modes(dev, mode, B, H, I, Kq, hd, sel):
     """The backward in split mode (f32 kernel: f32-accurate) and in bf16 mode (one-plane bf16 kernel)
     against the f64 reference, tail and selected queries."""
@@ -735,6 +754,14 @@ def test_attn_bwd_key_slices(dev, B, H, I, Kq, hd):
         assert torch.equal(p16[:, d:].cpu(), d16[:, d:].cpu())
         qa, qb_ = p16[:, :d].view(torch.bfloat16).float().cpu(), d16[:, :d].view(torch.bfloat16).float().cpu()
         assert (qa - qb_).abs().max().item() <= 2 ** -7 * qb_.abs().max().item()
+        # bf16 qkv (OT_ATTN_QKV_BF16): the kernel rounds f32 operands to bf16 itself, so operands that are bf16
+        # values already give the same dqkv from either form, bit for bit
+        q16 = qkv.to(torch.bfloat16)
+        r32, r16 = torch.zeros_like(dqkv), torch.zeros_like(dqkv)
+        K.attn_bwd(q16.float(), 3 * d, out, dout, lse, B, H, I, Kq, hd, r32)
+        K.attn_bwd(q16.view(torch.int16), 3 * d, out, dout, lse, B, H, I, Kq, hd, r16)
+        torch.cuda.synchronize()
+        assert torch.equal(r32.cpu(), r16.cpu())
     finally:
         K.set_matmul_mode(old)
 

@@ -101,12 +101,13 @@ def run_masked(dev, B, H, I, Kq, hd, valid, qpos=None, backward=True, seed=0):
     torch.testing.assert_close(dqkv.double().cpu(), qkv_r.grad, rtol=1e-4, atol=1e-4)
 
 
-@pytest.mark.parametrize('hd', [32, 64])
+@pytest.mark.parametrize('hd', [32, 64, 16, 128])
 @pytest.mark.parametrize('I', [37, 70])
 @pytest.mark.parametrize('Kq', ['I', 9, 3, 1])
 def test_masked_attention(dev, hd, I, Kq):
     """Forward (out, lse) and backward (dqkv), every row compared, padding queries included: the MFMA kernels
-    (K > 4; head_dim 64 backward as two 32-dim waves), the short-tail kernels (K = 3: KQ 4; K = 1: KQ 1)."""
+    (K > 4; head_dim 64 backward as two 32-dim waves), the short-tail kernels (K = 3: KQ 4; K = 1: KQ 1; at
+    head_dim 16 the forward stays on the MFMA kernel)."""
     B, H = 3, 2
     Kq = I if Kq == 'I' else Kq
     for name, valid in patterns(B, I).items():
@@ -120,12 +121,13 @@ def test_masked_attention_forward_other_head_dims(dev, hd):
 
 
 def test_masked_attention_selected_queries(dev):
-    """Queries at per-sample kept positions (the SEL backward, the forward's per-query positions)."""
-    B, H, I, Kq, hd = 3, 2, 70, 23, 32
+    """Queries at per-sample kept positions (the SEL backward, the forward's per-query positions), at every head_dim."""
+    B, H, I, Kq = 3, 2, 70, 23
     rng = np.random.default_rng(4)
     qpos = np.stack([np.append(np.sort(rng.choice(I - 1, Kq - 1, replace=False)), I - 1) for _ in range(B)])
-    for name, valid in patterns(B, I).items():
-        run_masked(dev, B, H, I, Kq, hd, valid, qpos=qpos)
+    for hd in (32, 16, 64, 128):
+        for name, valid in patterns(B, I).items():
+            run_masked(dev, B, H, I, Kq, hd, valid, qpos=qpos)
 
 
 def test_masked_attention_refuses_bf16(dev):
@@ -142,8 +144,14 @@ def test_masked_attention_refuses_bf16(dev):
 @pytest.mark.parametrize('Ic', [0, 40])
 @pytest.mark.parametrize('Kq', [4, 1])
 def test_masked_cached_attention(dev, Ic, Kq):
-    """The cached forward: candidates' N rows over their request's cached rows under cache_valid, own rows valid."""
-    R_, C, H, hd, n = 3, 5, 2, 32, 4
+    """The cached forward: candidates' N rows over their request's cached rows under cache_valid, own rows valid; at
+    every head_dim."""
+    for hd in (32, 16, 64, 128):
+        check_masked_cached(dev, Ic, Kq, hd)
+
+
+def check_masked_cached(dev, Ic, Kq, hd):
+    R_, C, H, n = 3, 5, 2, 4
     d = H * hd
     torch.manual_seed(1)
     req = np.array([0, 2, 1, 2, 0])
