@@ -724,6 +724,34 @@ int ot_task_loss_fwd(const float* probs, const float* labels, int T, int B, unsi
                      void* workspace, size_t ws_bytes, void* stream);
 int ot_task_loss_bwd(const float* probs, const float* labels, const float* gscale, int T, int B,
                      unsigned mse_mask, float* dprobs, void* stream);
+/* ---- weighted task loss (model_io.hip) ------------------------------------------------------
+ * Build extension (Keras's sample_weight / loss_weights; no reference site).  l[t][b] is the per-element term of
+ * the calls above: the logits-form BCE (logits given), the clipped probability-form BCE (logits NULL), or
+ * (y - p)^2 for a task whose bit is set in mse_mask.
+ *   weights      task t's B weights at + t * weight_stride; weight_stride 0 = one [B] row shared by all tasks,
+ *                otherwise >= B.  A weight is clamped to [0, OT_LOSS_WEIGHT_MAX]; a NaN or a negative value is 0.
+ *                A zero weight removes the entry by selection: its label and prediction do not enter the loss,
+ *                whatever they hold (NaN, +-inf), and its gradient is exactly 0.
+ *   task_scale   T coefficients a_t (device memory), or NULL for ones
+ *   reduction    OT_LOSS_REDUCE_BATCH:   loss = sum_t a_t (sum_b w l) / B     (Keras SUM_OVER_BATCH_SIZE)
+ *                OT_LOSS_REDUCE_WEIGHTS: loss = sum_t a_t (sum_b w l) / sum_b w; a task whose weights sum to 0
+ *                contributes loss 0 and gradient 0
+ *   denom        [T] floats, written by fwd (B or sum_b w) and read by bwd: no host sync in between
+ * fwd: grid (workgroups, T), per-task partials {sum w l, sum w} in the workspace
+ * (ot_task_loss_weighted_workspace_size), folded in index order in double: run-to-run bit-identical.
+ * bwd: dout[t][b] = gscale[0] a_t w dl/dz / denom_t (prob_form 0: to the logits) or ... dl/dp ... (prob_form 1: to
+ * the probabilities, 0 where p was clipped).  T <= 32, B >= 1. */
+#define OT_LOSS_REDUCE_BATCH 0
+#define OT_LOSS_REDUCE_WEIGHTS 1
+#define OT_LOSS_WEIGHT_MAX 65536
+size_t ot_task_loss_weighted_workspace_size(int T, int B);
+int ot_task_loss_weighted_fwd(const float* logits, const float* probs, const float* labels, const float* weights,
+                              int64_t weight_stride, const float* task_scale, int T, int B, unsigned mse_mask,
+                              int reduction, float* loss, float* denom, void* workspace, size_t ws_bytes,
+                              void* stream);
+int ot_task_loss_weighted_bwd(const float* probs, const float* labels, const float* weights, int64_t weight_stride,
+                              const float* task_scale, const float* denom, const float* gscale, int T, int B,
+                              unsigned mse_mask, int prob_form, float* dout, void* stream);
 
 /* ---- sparse embedding update (embedding.hip) ----------------------------------------------
  * Build extension (no reference site; paper: sparse Adagrad, clip 120, complete_translation.md:190).
@@ -836,6 +864,21 @@ size_t ot_metrics_workspace_size(int T, int B);
 int ot_metrics_update(const float* probs, const float* labels, int T, int B, int64_t task_stride,
                       const double* bounds, int nb, int64_t* counts, double* sums, void* workspace,
                       size_t ws_bytes, void* stream);
+/* The weighted sibling (Keras metrics under sample_weight): the same walk with a third operand.
+ *   weights        task t's B weights at + t * weight_stride (0 = one [B] row for every task, otherwise >= B),
+ *                  clamped to [0, 2^16] (NaN, negatives: 0) and rounded to the nearest multiple of 2^-24: u units,
+ *                  OT_METRICS_WEIGHT_ONE units = weight 1.  A sample of 0 units is skipped whatever it holds.
+ *   counts         += u per sample instead of 1 (a per-workgroup 64-bit LDS histogram, touched bins flushed with
+ *                  64-bit integer atomics): exact and commutative like the un-weighted state
+ *   sums           += {sum u (added as integers per call), sum u (p-y)^2, sum u |p-y|, sum u bce}; the last three in
+ *                  double in the fixed order above; no float atomics
+ * A state updated this way is in units throughout: every reported ratio is the un-weighted formula on it.  Exact
+ * while a window's sum of weights stays under 2^29 (sum u < 2^53).  Workspace: ot_metrics_weighted_workspace_size. */
+#define OT_METRICS_WEIGHT_ONE (1 << 24)
+size_t ot_metrics_weighted_workspace_size(int T, int B);
+int ot_metrics_update_weighted(const float* probs, const float* labels, const float* weights, int T, int B,
+                               int64_t task_stride, int64_t weight_stride, const double* bounds, int nb,
+                               int64_t* counts, double* sums, void* workspace, size_t ws_bytes, void* stream);
 
 /* ---- grouped AUC (metrics_grouped.hip) -----------------------------------------------------
  * The impression-weighted user-level AUC (UAUC) of the paper (complete_translation.md:178-180) over

@@ -32,6 +32,10 @@ OT_FP8_DEQUANT, OT_FP8_TWO_TERM = 1, 2
 OT_RANK_SUM, OT_RANK_PRODUCT = 0, 1
 RANK_MODES = {'sum': OT_RANK_SUM, 'product': OT_RANK_PRODUCT}
 RANK_MAX_K = 1024
+OT_LOSS_REDUCE_BATCH, OT_LOSS_REDUCE_WEIGHTS = 0, 1
+LOSS_REDUCTIONS = {'batch': OT_LOSS_REDUCE_BATCH, 'weights': OT_LOSS_REDUCE_WEIGHTS}
+OT_LOSS_WEIGHT_MAX = 65536              # weights live in [0, 2^16] ...
+OT_METRICS_WEIGHT_ONE = 1 << 24         # ... and the metrics count them in units of 2^-24
 MATMUL_MODES = {'f32': OT_MATMUL_F32, 'split': OT_MATMUL_SPLIT_BF16, 'bf16': OT_MATMUL_BF16}
 
 
@@ -193,6 +197,9 @@ SIGNATURES = {
     'ot_task_loss_bwd': (c_int, [P, P, P, c_int, c_int, c_uint32, P, P]),
     'ot_task_loss_logits_fwd': (c_int, [P, P, P, c_int, c_int, c_uint32, P, P, c_size_t, P]),
     'ot_task_loss_logits_bwd': (c_int, [P, P, P, c_int, c_int, c_uint32, P, P]),
+    'ot_task_loss_weighted_workspace_size': (c_size_t, [c_int, c_int]),
+    'ot_task_loss_weighted_fwd': (c_int, [P, P, P, P, I64, P, c_int, c_int, c_uint32, c_int, P, P, P, c_size_t, P]),
+    'ot_task_loss_weighted_bwd': (c_int, [P, P, P, I64, P, P, P, c_int, c_int, c_uint32, c_int, P, P]),
     'ot_head_bwd_ex': (c_int, [P, P, P, P, P, c_int, c_int, c_int, P, P, P, I64, I64, c_int, P, c_size_t, P]),
     'ot_sparse_adagrad_workspace_size': (c_size_t, [I64, c_int]),
     'ot_sparse_adagrad': (c_int, [P, P, c_int, I64, P, P, I64, c_float, c_float, c_float, P, c_size_t, P]),
@@ -219,6 +226,8 @@ SIGNATURES = {
                              c_size_t, P]),
     'ot_metrics_workspace_size': (c_size_t, [c_int, c_int]),
     'ot_metrics_update': (c_int, [P, P, c_int, c_int, I64, P, c_int, P, P, P, c_size_t, P]),
+    'ot_metrics_weighted_workspace_size': (c_size_t, [c_int, c_int]),
+    'ot_metrics_update_weighted': (c_int, [P, P, P, c_int, c_int, I64, I64, P, c_int, P, P, P, c_size_t, P]),
     'ot_grouped_auc_workspace_size': (c_size_t, [c_int, I64, c_int]),
     'ot_grouped_auc': (c_int, [P, P, P, c_int, I64, I64, c_int, c_uint32, P, P, P, P, P, c_size_t, P]),
     'ot_rank_topk_workspace_size': (c_size_t, [c_int, I64, c_int]),

@@ -130,6 +130,18 @@ class OneTransConfig:
         # own Dense(F_g -> d) to become token g
         self.ns_tokenizer = 'auto'
         self.ns_token_groups: List[List[str]] = []
+        # build: weighted and partially labelled multi-task training.  Off (the reference): every
+        # sample counts once in every task and nothing new is read.  On: the labels dict may carry
+        # ``labels[sample_weight_key]`` and ``labels[task + label_weight_suffix]`` ([B] or [B, 1], in [0, 65536]); task
+        # t weighs sample b by their product (a missing factor is 1, a zero removes the entry, whose label may then be
+        # NaN), in the loss, its gradient and the running metrics.  ``task_loss_weights`` {task: a_t} scales a task's
+        # loss term (never a metric; a missing task is 1).  ``loss_reduction``: 'batch' divides a task's weighted sum
+        # by B (Keras SUM_OVER_BATCH_SIZE with sample_weight), 'weights' by the task's sum of weights
+        self.weighted_loss = False
+        self.loss_reduction = 'batch'
+        self.task_loss_weights: Dict[str, float] = {}
+        self.sample_weight_key = 'sample_weight'
+        self.label_weight_suffix = '_weight'
 
     # ------------------------------------------------------------------ helpers
     def to_dict(self) -> Dict:
@@ -327,6 +339,38 @@ def check_seq_fusion(cfg: OneTransConfig) -> None:
         raise ValueError(f"unknown seq_fusion {mode!r}: expected 'sep' or 'time'")
     if mode == 'time' and not getattr(cfg, 'seq_time_suffix', '_time'):
         raise ValueError("seq_fusion='time' needs a non-empty seq_time_suffix")
+
+
+LOSS_REDUCTIONS = ('batch', 'weights')
+LOSS_WEIGHT_MAX = 65536.0            # a sample / task weight lives in [0, 2^16] (ot_task_loss_weighted_*)
+
+
+def check_weighted_loss(cfg: OneTransConfig) -> None:
+    """``loss_reduction`` is 'batch' or 'weights'; every ``task_loss_weights`` key names a task and its value is a
+    finite number >= 0; the two weight-key names are non-empty and distinct from the task names.  Nothing is checked
+    while ``weighted_loss`` is off (none of these fields is then read)."""
+    if not getattr(cfg, 'weighted_loss', False):
+        return
+    red = getattr(cfg, 'loss_reduction', 'batch')
+    if red not in LOSS_REDUCTIONS:
+        raise ValueError(f"unknown loss_reduction {red!r}: expected 'batch' or 'weights'")
+    for t, a in (getattr(cfg, 'task_loss_weights', None) or {}).items():
+        if t not in cfg.tasks:
+            raise ValueError(f'task_loss_weights names {t!r}, which is not a task (tasks: {list(cfg.tasks)})')
+        if isinstance(a, bool) or not isinstance(a, (int, float)) or not math.isfinite(a) or a < 0:
+            raise ValueError(f'task_loss_weights[{t!r}] = {a!r}: a finite number >= 0 expected')
+    key, suf = getattr(cfg, 'sample_weight_key', 'sample_weight'), getattr(cfg, 'label_weight_suffix', '_weight')
+    if not key or not suf:
+        raise ValueError('weighted_loss needs a non-empty sample_weight_key and label_weight_suffix')
+    if key in cfg.tasks or any(t + suf in cfg.tasks for t in cfg.tasks):
+        raise ValueError('sample_weight_key / label_weight_suffix collide with a task name')
+
+
+def task_loss_scale(cfg: OneTransConfig):
+    """[a_t for t in tasks] from ``task_loss_weights``, or None when every coefficient is 1."""
+    tw = getattr(cfg, 'task_loss_weights', None) or {}
+    a = [float(tw.get(t, 1.0)) for t in cfg.tasks]
+    return None if all(v == 1.0 for v in a) else a
 
 
 def check_padding_mask(cfg: OneTransConfig) -> None:

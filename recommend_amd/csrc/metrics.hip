@@ -105,6 +105,110 @@ __global__ void metrics_fold_kernel(const double* __restrict__ part, int nblk, i
   }
 }
 
+// ---- the weighted sibling (ot_metrics_update_weighted) ----
+// A weight is clamped to [0, 2^16] (NaN and negatives: 0) and rounded to the nearest multiple of 2^-24 (ties to
+// even): the count of such units, an integer <= 2^40.  The histogram and sum w are integers in those units, so the
+// state stays exact and commutative.
+__device__ __forceinline__ unsigned long long metrics_weight_units(float w) {
+  const float c = w > 0.f ? fminf(w, 65536.f) : 0.f;
+  return (unsigned long long)__double2ll_rn((double)c * (double)OT_METRICS_WEIGHT_ONE);
+}
+
+// metrics_sample under a weight of u units: nothing at all for u == 0 (the entry is skipped, whatever it holds)
+__device__ __forceinline__ void metrics_sample_weighted(float pf, float yf, unsigned long long u, const double* sb,
+                                                        int nb, unsigned long long* hist, MetricAcc& a,
+                                                        unsigned long long& wsum) {
+  if (u == 0ull) return;
+  const double p = (double)pf, y = (double)yf, w = (double)u;
+  int lo = 0, hi = nb;
+  while (lo < hi) {
+    const int mid = (lo + hi) >> 1;
+    if (sb[mid] < p) lo = mid + 1;
+    else hi = mid;
+  }
+  atomicAdd(&hist[(yf > 0.5f ? nb + 1 : 0) + lo], u);
+  wsum += u;
+  const double d = p - y;
+  a.se += w * (d * d);
+  a.ae += w * fabs(d);
+  const double eps = 1e-7;
+  const double pc = p < eps ? eps : (p > 1.0 - eps ? 1.0 - eps : p);
+  a.bce += w * -(y * log(pc + eps) + (1.0 - y) * log(1.0 - pc + eps));
+}
+
+// The quad walk of metrics_update_kernel with a third operand: task t's weights at weights + t * weight_stride
+// (stride 0: one row for every task).  part as above; wpart[t*gridDim.x + g] = this workgroup's sum of units.
+template <bool VEC>
+__global__ __launch_bounds__(256) void metrics_update_weighted_kernel(
+    const float* __restrict__ probs, const float* __restrict__ labels, const float* __restrict__ weights, int B,
+    int64_t task_stride, int64_t weight_stride, const double* __restrict__ bounds, int nb, unsigned long long* counts,
+    double* part, unsigned long long* wpart) {
+  __shared__ double sb[METRICS_MAX_NB];
+  __shared__ unsigned long long hist[2 * (METRICS_MAX_NB + 1)];
+  __shared__ double red[4][3];
+  __shared__ unsigned long long wtot;
+  const int t = blockIdx.y, tid = threadIdx.x;
+  const int nh = 2 * (nb + 1);
+  for (int i = tid; i < nb; i += 256) sb[i] = bounds[i];
+  for (int i = tid; i < nh; i += 256) hist[i] = 0ull;
+  if (tid == 0) wtot = 0ull;
+  __syncthreads();
+  const float* p = probs + (int64_t)t * task_stride;
+  const float* y = labels + (int64_t)t * task_stride;
+  const float* w = weights + (int64_t)t * weight_stride;
+  const int64_t nquad = ((int64_t)B + 3) >> 2;
+  MetricAcc a = {0.0, 0.0, 0.0};
+  unsigned long long wsum = 0ull;
+  for (int64_t q = (int64_t)blockIdx.x * 256 + tid; q < nquad; q += (int64_t)gridDim.x * 256) {
+    const int64_t i0 = q << 2;
+    if (VEC && i0 + 3 < B) {
+      const f32x4 pv = *reinterpret_cast<const f32x4*>(p + i0);
+      const f32x4 yv = *reinterpret_cast<const f32x4*>(y + i0);
+      const f32x4 wv = *reinterpret_cast<const f32x4*>(w + i0);
+#pragma unroll
+      for (int k = 0; k < 4; ++k) metrics_sample_weighted(pv[k], yv[k], metrics_weight_units(wv[k]), sb, nb, hist, a, wsum);
+    } else {
+      for (int k = 0; k < 4; ++k)
+        if (i0 + k < B)
+          metrics_sample_weighted(p[i0 + k], y[i0 + k], metrics_weight_units(w[i0 + k]), sb, nb, hist, a, wsum);
+    }
+  }
+  if (wsum) atomicAdd(&wtot, wsum);            // integer: exact in any order
+  a.se = wave_sum(a.se);
+  a.ae = wave_sum(a.ae);
+  a.bce = wave_sum(a.bce);
+  if ((tid & 63) == 0) {
+    red[tid >> 6][0] = a.se;
+    red[tid >> 6][1] = a.ae;
+    red[tid >> 6][2] = a.bce;
+  }
+  __syncthreads();
+  const int64_t slot = (int64_t)t * gridDim.x + blockIdx.x;
+  if (tid < 3) part[slot * 3 + tid] = (red[0][tid] + red[1][tid]) + (red[2][tid] + red[3][tid]);
+  if (tid == 3) wpart[slot] = wtot;
+  unsigned long long* c = counts + (int64_t)t * nh;
+  for (int i = tid; i < nh; i += 256) {
+    const unsigned long long v = hist[i];
+    if (v) atomicAdd(&c[i], v);
+  }
+}
+
+// grid T, 64 threads: sums[t] += {the workgroups' units added as integers, the partials folded in index order}
+__global__ void metrics_fold_weighted_kernel(const double* __restrict__ part, const unsigned long long* __restrict__ wpart,
+                                             int nblk, double* sums) {
+  const int t = blockIdx.x, k = threadIdx.x;
+  if (k == 0) {
+    unsigned long long s = 0ull;
+    for (int g = 0; g < nblk; ++g) s += wpart[(int64_t)t * nblk + g];
+    sums[t * 4] += (double)s;
+  }
+  if (k >= 1 && k <= 3) {
+    double s = 0.0;
+    for (int g = 0; g < nblk; ++g) s += part[((int64_t)t * nblk + g) * 3 + (k - 1)];
+    sums[t * 4 + k] += s;
+  }
+}
+
 }  // namespace ot
 
 using namespace ot;
@@ -137,5 +241,43 @@ extern "C" int ot_metrics_update(const float* probs, const float* labels, int T,
   hipLaunchKernelGGL(metrics_fold_kernel, dim3(T), dim3(64), 0, (hipStream_t)stream, (const double*)workspace, nblk, B,
                      sums);
   OT_LAUNCH_CHECK("ot_metrics_update(fold)");
+  return OT_OK;
+}
+
+extern "C" size_t ot_metrics_weighted_workspace_size(int T, int B) {
+  if (T < 1 || B < 1) return 0;
+  return (size_t)T * metrics_blocks(B) * (3 * sizeof(double) + sizeof(unsigned long long));
+}
+
+extern "C" int ot_metrics_update_weighted(const float* probs, const float* labels, const float* weights, int T, int B,
+                                          int64_t task_stride, int64_t weight_stride, const double* bounds, int nb,
+                                          int64_t* counts, double* sums, void* workspace, size_t ws_bytes,
+                                          void* stream) {
+  OT_REQUIRE(probs && labels && weights && bounds && counts && sums && workspace,
+             "ot_metrics_update_weighted: null operand");
+  OT_REQUIRE(T > 0 && T <= 32, "ot_metrics_update_weighted: 1..32 tasks");
+  OT_REQUIRE(nb > 0 && nb <= METRICS_MAX_NB, "ot_metrics_update_weighted: 1..%d thresholds", METRICS_MAX_NB);
+  OT_REQUIRE(B > 0, "ot_metrics_update_weighted: empty batch");
+  OT_REQUIRE(task_stride >= B, "ot_metrics_update_weighted: task_stride < B");
+  OT_REQUIRE(weight_stride == 0 || weight_stride >= B, "ot_metrics_update_weighted: weight_stride is 0 or >= B");
+  OT_REQUIRE(ws_bytes >= ot_metrics_weighted_workspace_size(T, B), "ot_metrics_update_weighted: workspace too small");
+  OT_REQUIRE((reinterpret_cast<uintptr_t>(probs) & 3) == 0 && (reinterpret_cast<uintptr_t>(labels) & 3) == 0 &&
+                 (reinterpret_cast<uintptr_t>(weights) & 3) == 0 && (reinterpret_cast<uintptr_t>(bounds) & 7) == 0 &&
+                 (reinterpret_cast<uintptr_t>(counts) & 7) == 0 && (reinterpret_cast<uintptr_t>(sums) & 7) == 0 &&
+                 (reinterpret_cast<uintptr_t>(workspace) & 7) == 0,
+             "ot_metrics_update_weighted: misaligned operand");
+  const int nblk = metrics_blocks(B);
+  const bool vec = ((reinterpret_cast<uintptr_t>(probs) | reinterpret_cast<uintptr_t>(labels) |
+                     reinterpret_cast<uintptr_t>(weights)) & 15) == 0 &&
+                   (T == 1 || ((task_stride | weight_stride) & 3) == 0);
+  double* part = (double*)workspace;
+  unsigned long long* wpart = reinterpret_cast<unsigned long long*>(part + (size_t)T * nblk * 3);
+  auto kern = vec ? metrics_update_weighted_kernel<true> : metrics_update_weighted_kernel<false>;
+  hipLaunchKernelGGL(kern, dim3(nblk, T), dim3(256), 0, (hipStream_t)stream, probs, labels, weights, B, task_stride,
+                     weight_stride, bounds, nb, reinterpret_cast<unsigned long long*>(counts), part, wpart);
+  OT_LAUNCH_CHECK("ot_metrics_update_weighted");
+  hipLaunchKernelGGL(metrics_fold_weighted_kernel, dim3(T), dim3(64), 0, (hipStream_t)stream, (const double*)part,
+                     (const unsigned long long*)wpart, nblk, sums);
+  OT_LAUNCH_CHECK("ot_metrics_update_weighted(fold)");
   return OT_OK;
 }

@@ -7,6 +7,8 @@
 //   ot_head_fwd/bwd  task heads model.py:325-330, 388-391 (second Dense(1, sigmoid) + sigmoid)
 //   ot_bce_fwd/bwd   tf.keras.losses.BinaryCrossentropy(from_logits=False) train.py:84-87,124-128
 //   ot_task_loss_*   per-task BCE ('ctr'/'cvr') or MeanSquaredError (other tasks) train.py:78-93
+//   ot_task_loss_weighted_*  the same terms under per-(task, sample) weights, task coefficients and Keras's
+//                    sample_weight reductions (build extension)
 #include "common.h"
 
 namespace ot {
@@ -201,6 +203,97 @@ __global__ void loss_z_bwd_kernel(const float* __restrict__ probs, const float* 
   dlogits[i] = g * invB * gscale[0];
 }
 
+// ---- the weighted task loss (include/onetrans_hip.h, "weighted task loss") ----
+// A weight outside [0, OT_LOSS_WEIGHT_MAX] is clamped: a NaN or a negative value counts as 0 (every compare with a
+// NaN is false), anything above the range as the range's end.
+__device__ __forceinline__ float loss_weight(float w) { return w > 0.f ? fminf(w, 65536.f) : 0.f; }
+
+// grid (nblk, T): workgroup (g, t) takes the samples b = g*256 + tid, + nblk*256, ... of task t.  A zero weight
+// SELECTS the entry out (its label and prediction are never read into the sum, so a NaN label or an infinite logit
+// there is harmless).  part[(t*nblk + g)*2 + {0, 1}] = this workgroup's {sum w l, sum w}: f32 terms, summed in double
+// from the thread on (thread -> wave -> workgroup, fixed order).
+__global__ __launch_bounds__(256) void loss_w_fwd_kernel(const float* __restrict__ logits, const float* __restrict__ probs,
+                                                         const float* __restrict__ labels,
+                                                         const float* __restrict__ weights, int64_t wstride, int B,
+                                                         unsigned mse_mask, double* part) {
+  __shared__ double red[4][2];
+  const int t = blockIdx.y, tid = threadIdx.x;
+  const bool mse = (mse_mask >> t) & 1u;
+  const float* w = weights + (int64_t)t * wstride;
+  const int64_t row = (int64_t)t * B;
+  double sl = 0.0, sw = 0.0;
+  for (int64_t b = (int64_t)blockIdx.x * 256 + tid; b < B; b += (int64_t)gridDim.x * 256) {
+    const float wb = loss_weight(w[b]);
+    if (wb > 0.f) {
+      const float y = labels[row + b];
+      float l;
+      if (mse) { const float e = probs[row + b] - y; l = e * e; }
+      else l = logits ? bce_logits(y, logits[row + b]) : keras_bce(y, probs[row + b]);
+      sl += (double)(wb * l);
+      sw += (double)wb;
+    }
+  }
+  const double dl = wave_sum(sl), dw = wave_sum(sw);
+  if ((tid & 63) == 0) { red[tid >> 6][0] = dl; red[tid >> 6][1] = dw; }
+  __syncthreads();
+  if (tid < 2) part[((int64_t)t * gridDim.x + blockIdx.x) * 2 + tid] = (red[0][tid] + red[1][tid]) + (red[2][tid] + red[3][tid]);
+}
+
+// one workgroup of 64: thread t < T folds task t's partials in index order, writes denom[t] (B for the 'batch'
+// reduction, sum w for 'weights') and its term a_t * (sum w l) / denom_t (0 when the denominator is 0); thread 0
+// then adds the terms in task order
+__global__ void loss_w_fold_kernel(const double* __restrict__ part, int nblk, int T, int B, int reduction,
+                                   const float* __restrict__ task_scale, float* loss, float* denom) {
+  __shared__ double term[32];
+  const int t = threadIdx.x;
+  if (t < T) {
+    double sl = 0.0, sw = 0.0;
+    for (int g = 0; g < nblk; ++g) {
+      sl += part[((int64_t)t * nblk + g) * 2];
+      sw += part[((int64_t)t * nblk + g) * 2 + 1];
+    }
+    const float den = reduction == OT_LOSS_REDUCE_WEIGHTS ? (float)sw : (float)B;
+    denom[t] = den;
+    term[t] = den > 0.f ? (double)(task_scale ? task_scale[t] : 1.f) * sl / (double)den : 0.0;
+  }
+  __syncthreads();
+  if (t == 0) {
+    double s = 0.0;
+    for (int i = 0; i < T; ++i) s += term[i];
+    loss[0] = (float)s;
+  }
+}
+
+// grid (ceil(B / 256), T): dout = gscale a_t w (dl/dz or dl/dp) / denom_t, exactly 0 for a zero weight or an empty
+// denominator.  PROB: the gradient of the probability form (to the probabilities), else of the logits form
+template <bool PROB>
+__global__ void loss_w_bwd_kernel(const float* __restrict__ probs, const float* __restrict__ labels,
+                                  const float* __restrict__ weights, int64_t wstride,
+                                  const float* __restrict__ task_scale, const float* __restrict__ denom,
+                                  const float* __restrict__ gscale, int B, unsigned mse_mask, float* dout) {
+  const int t = blockIdx.y;
+  const int64_t b = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (b >= B) return;
+  const int64_t i = (int64_t)t * B + b;
+  const float wb = loss_weight(weights[(int64_t)t * wstride + b]);
+  const float den = denom[t];
+  float g = 0.f;
+  if (wb > 0.f && den > 0.f) {
+    const float p = probs[i], y = labels[i];
+    const bool mse = (mse_mask >> t) & 1u;
+    float d;
+    if (PROB) {
+      const float eps = 1e-7f;
+      if (mse) d = 2.f * (p - y);
+      else d = (p >= eps && p <= 1.f - eps) ? -y / (p + eps) + (1.f - y) / (1.f - p + eps) : 0.f;
+    } else {
+      d = mse ? 2.f * (p - y) * p * (1.f - p) : p - y;
+    }
+    g = (gscale[0] * (task_scale ? task_scale[t] : 1.f) * wb / den) * d;
+  }
+  dout[i] = g;
+}
+
 inline int bce_blocks(int64_t n) {
   int64_t b = (n + 255) / 256;
   return (int)(b < 256 ? (b < 1 ? 1 : b) : 256);
@@ -348,6 +441,49 @@ extern "C" int ot_task_loss_logits_bwd(const float* probs, const float* labels, 
   hipLaunchKernelGGL(loss_z_bwd_kernel, dim3(ceil_div(n, 256)), dim3(256), 0, (hipStream_t)stream, probs, labels,
                      gscale, n, B, 1.f / B, mse_mask, dlogits);
   OT_LAUNCH_CHECK("ot_task_loss_logits_bwd");
+  return OT_OK;
+}
+
+extern "C" size_t ot_task_loss_weighted_workspace_size(int T, int B) {
+  if (T < 1 || B < 1) return 0;
+  return (size_t)T * bce_blocks(B) * 2 * sizeof(double);
+}
+
+extern "C" int ot_task_loss_weighted_fwd(const float* logits, const float* probs, const float* labels,
+                                         const float* weights, int64_t weight_stride, const float* task_scale, int T,
+                                         int B, unsigned mse_mask, int reduction, float* loss, float* denom,
+                                         void* workspace, size_t ws_bytes, void* stream) {
+  OT_REQUIRE(probs && labels && weights && loss && denom && workspace, "ot_task_loss_weighted_fwd: null operand");
+  OT_REQUIRE(B > 0, "ot_task_loss_weighted_fwd: empty batch");
+  OT_REQUIRE(T > 0 && T <= 32, "ot_task_loss_weighted_fwd: 1..32 tasks");
+  OT_REQUIRE(reduction == OT_LOSS_REDUCE_BATCH || reduction == OT_LOSS_REDUCE_WEIGHTS,
+             "ot_task_loss_weighted_fwd: unknown reduction %d", reduction);
+  OT_REQUIRE(weight_stride == 0 || weight_stride >= B, "ot_task_loss_weighted_fwd: weight_stride is 0 or >= B");
+  OT_REQUIRE(ws_bytes >= ot_task_loss_weighted_workspace_size(T, B) &&
+                 (reinterpret_cast<uintptr_t>(workspace) & 7) == 0,
+             "ot_task_loss_weighted_fwd: workspace too small or misaligned");
+  const int nblk = bce_blocks(B);
+  hipLaunchKernelGGL(loss_w_fwd_kernel, dim3(nblk, T), dim3(256), 0, (hipStream_t)stream, logits, probs, labels,
+                     weights, weight_stride, B, mse_mask, (double*)workspace);
+  OT_LAUNCH_CHECK("ot_task_loss_weighted_fwd");
+  hipLaunchKernelGGL(loss_w_fold_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, (const double*)workspace, nblk, T,
+                     B, reduction, task_scale, loss, denom);
+  OT_LAUNCH_CHECK("ot_task_loss_weighted_fwd(fold)");
+  return OT_OK;
+}
+
+extern "C" int ot_task_loss_weighted_bwd(const float* probs, const float* labels, const float* weights,
+                                         int64_t weight_stride, const float* task_scale, const float* denom,
+                                         const float* gscale, int T, int B, unsigned mse_mask, int prob_form,
+                                         float* dout, void* stream) {
+  OT_REQUIRE(probs && labels && weights && denom && gscale && dout, "ot_task_loss_weighted_bwd: null operand");
+  OT_REQUIRE(B > 0, "ot_task_loss_weighted_bwd: empty batch");
+  OT_REQUIRE(T > 0 && T <= 32, "ot_task_loss_weighted_bwd: 1..32 tasks");
+  OT_REQUIRE(weight_stride == 0 || weight_stride >= B, "ot_task_loss_weighted_bwd: weight_stride is 0 or >= B");
+  auto kern = prob_form ? loss_w_bwd_kernel<true> : loss_w_bwd_kernel<false>;
+  hipLaunchKernelGGL(kern, dim3(ceil_div(B, 256), T), dim3(256), 0, (hipStream_t)stream, probs, labels, weights,
+                     weight_stride, task_scale, denom, gscale, B, mse_mask, dout);
+  OT_LAUNCH_CHECK("ot_task_loss_weighted_bwd");
   return OT_OK;
 }
 

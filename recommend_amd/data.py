@@ -23,6 +23,10 @@
 * ``ragged_lengths`` — history lengths for ``config.seq_padding_mask`` (``name + config.seq_len_suffix``, int32
   ``[B]``; empty and full histories both occur), for tests and tools/padmask_bench.py.  ``make_batch`` itself emits none.
 
+* ``gate_task_weights`` / ``downsample_negatives`` — host helpers for ``config.weighted_loss``: a task weight gated
+  on another task's label (conversion labels exist on clicked impressions only), and negative down-sampling with the
+  kept negatives re-weighted by ``1 / keep_rate``.
+
 All generators are numpy ``Generator(PCG64)``: same seed => same batch, here and
 on the GPU box.
 """
@@ -242,3 +246,42 @@ def expand_requests(batch: RequestBatch) -> Batch:
     ns, seq, labels, req = batch
     idx = np.asarray(req, dtype=np.int64)
     return ns, {k: np.asarray(v)[idx] for k, v in seq.items()}, labels
+
+
+def gate_task_weights(labels: Dict[str, np.ndarray], task: str = 'cvr', gate: str = 'ctr',
+                      suffix: str = '_weight') -> Dict[str, np.ndarray]:
+    """A copy of ``labels`` with ``labels[task + suffix]`` = 1 where ``labels[gate] > 0.5`` and 0 elsewhere (float32,
+    the gate's shape): under ``config.weighted_loss`` task ``task`` then trains and is measured on the gated rows
+    only — a CVR head on clicked impressions — and its label elsewhere is never read (it may be NaN)."""
+    if task not in labels or gate not in labels:
+        raise KeyError(f'gate_task_weights: labels hold {sorted(labels)}, not both {task!r} and {gate!r}')
+    out = dict(labels)
+    out[task + suffix] = (np.asarray(labels[gate]) > 0.5).astype(np.float32)
+    return out
+
+
+def downsample_negatives(batch, task: str, keep_rate: float, seed: int, weight_key: str = 'sample_weight'):
+    """Negative down-sampling of a host batch: every row whose ``labels[task]`` is not > 0.5 is kept with probability
+    ``keep_rate`` (numpy PCG64 of ``seed``), every positive is kept; ``labels[weight_key]`` of the result is
+    ``1 / keep_rate`` on the kept negatives and 1 on the positives (times the batch's own weight, if it has one), so
+    the weighted loss and metrics estimate those of the full stream.  Every array of ``non_seq``, ``seq`` and
+    ``labels`` is cut to the kept rows; in a request-grouped 4-tuple the candidate side (``non_seq``, ``labels``,
+    ``req``) is cut and the request side stays."""
+    if not 0.0 < float(keep_rate) <= 1.0:
+        raise ValueError(f'downsample_negatives: keep_rate {keep_rate!r} not in (0, 1]')
+    ns, seq, labels = batch[0], batch[1], batch[2]
+    y = np.asarray(labels[task]).reshape(-1)
+    rng = np.random.Generator(np.random.PCG64([int(seed), 0x6E6567]))
+    neg = ~(y > 0.5)
+    keep = ~neg | (rng.random(len(y)) < float(keep_rate))
+    rows = np.nonzero(keep)[0]
+    cut = lambda d: {k: np.asarray(v)[rows] for k, v in d.items()}
+    lab = cut(labels)
+    shape = np.asarray(labels[task]).shape
+    w = np.where(neg, np.float32(1.0 / float(keep_rate)), np.float32(1.0)).astype(np.float32).reshape(shape)[rows]
+    if weight_key in labels:
+        w = (w.reshape(-1) * np.asarray(labels[weight_key], dtype=np.float32).reshape(-1)[rows]).reshape(w.shape)
+    lab[weight_key] = w.astype(np.float32)
+    if len(batch) == 4:
+        return cut(ns), dict(seq), lab, np.asarray(batch[3])[rows]
+    return cut(ns), cut(seq), lab

@@ -17,7 +17,7 @@ import torch
 from .config import OneTransConfig
 from .metrics import GroupedAUC, StreamingMetrics
 from .model import OneTransModel
-from .trainer import _seq_inputs, _to_dev, stack_labels
+from .trainer import _seq_inputs, _to_dev, stack_labels, stack_weights
 
 
 class OneTransEvaluator:
@@ -31,7 +31,9 @@ class OneTransEvaluator:
         self.model = model
         self.config = config
         self.device = model.flat.device
-        self.metrics = StreamingMetrics(config.tasks, self.device, num_thresholds)
+        # config.weighted_loss: the batches' weight keys (trainer.stack_weights) weigh every metric
+        self.weighted = bool(getattr(config, 'weighted_loss', False))
+        self.metrics = StreamingMetrics(config.tasks, self.device, num_thresholds, weighted=self.weighted)
         self.group_feature = group_feature
         self.grouped = GroupedAUC(config.tasks, self.device) if group_feature is not None else None
 
@@ -54,8 +56,15 @@ class OneTransEvaluator:
         t0 = time.perf_counter()
         for non_seq, seq, labels in batches:
             y = labels if isinstance(labels, torch.Tensor) else stack_labels(labels, self.config.tasks, dev)
+            w = stack_weights(labels, self.config, dev) if self.weighted else None
+            if w is not None and self.grouped is not None:
+                raise NotImplementedError('weighted_loss with group_feature: the grouped AUC (UAUC) carries no sample '
+                                          'weights; drop the weight keys or the group feature')
             probs = self.model.forward_probs(_to_dev(non_seq, dev), _seq_inputs(self.model, seq, dev), training=False)
-            self.metrics.update(y, probs)
+            if self.weighted:
+                self.metrics.update(y, probs, weights=w)
+            else:
+                self.metrics.update(y, probs)
             if self.grouped is not None:
                 if self.group_feature not in non_seq:
                     raise KeyError(f'OneTransEvaluator(group_feature={self.group_feature!r}): the batch has no '

@@ -861,6 +861,19 @@ def metrics_update(probs, labels, T, B, task_stride, bounds, nb, counts, sums, d
         _probe.end('metrics', 0.0, ev)
 
 
+def metrics_update_weighted(probs, labels, weights, T, B, task_stride, weight_stride, bounds, nb, counts, sums,
+                            device=None) -> None:
+    """``metrics_update`` under per-sample weights (Keras metrics with ``sample_weight``): task t's weights at
+    ``weights + t * weight_stride`` (0: one [B] row for all tasks).  The state is then in units of 2^-24
+    (``_lib.OT_METRICS_WEIGHT_ONE`` per unit weight); a zero weight skips the sample."""
+    ws = workspace(size('ot_metrics_weighted_workspace_size', T, B), device)
+    ev = _probe.begin() if _probe is not None else None
+    call('ot_metrics_update_weighted', ptr(probs), ptr(labels), ptr(weights), T, B, task_stride, weight_stride,
+         ptr(bounds), nb, ptr(counts), ptr(sums), ptr(ws), ws.numel(), stream())
+    if ev is not None:
+        _probe.end('metrics', 0.0, ev)
+
+
 def grouped_auc(groups, scores, labels, T, n, task_stride, group_bits, task_mask, agg, num_groups, group_ids=None,
                 group_stats=None, device=None) -> None:
     """ot_grouped_auc over ``n`` records: ``agg`` [T, 4] float64 {Σ n_u·AUC_u, Σ AUC_u, Σ n_u, #valid groups},
@@ -998,6 +1011,29 @@ def task_loss_logits_fwd(logits, probs, labels, T, B, loss, device=None, mse_mas
 def task_loss_logits_bwd(probs, labels, gscale, T, B, dlogits, mse_mask: int = 0) -> None:
     ev = _probe.begin() if _probe is not None else None
     call('ot_task_loss_logits_bwd', ptr(probs), ptr(labels), ptr(gscale), T, B, mse_mask, ptr(dlogits), stream())
+    if ev is not None:
+        _probe.end('head_loss', 0.0, ev)
+
+
+def task_loss_weighted_fwd(logits, probs, labels, weights, weight_stride, task_scale, T, B, loss, denom, device=None,
+                           mse_mask: int = 0, reduction: str = 'batch') -> None:
+    """Σ_t a_t (Σ_b w l) / denom_t with l the per-element term of the un-weighted calls (``logits`` None: the
+    probability form), ``denom_t`` = B ('batch') or Σ_b w ('weights').  Writes ``loss`` [1] and ``denom`` [T]."""
+    ws = workspace(size('ot_task_loss_weighted_workspace_size', T, B), device)
+    ev = _probe.begin() if _probe is not None else None
+    call('ot_task_loss_weighted_fwd', ptr(logits), ptr(probs), ptr(labels), ptr(weights), weight_stride,
+         ptr(task_scale), T, B, mse_mask, _lib.LOSS_REDUCTIONS[reduction], ptr(loss), ptr(denom), ptr(ws), ws.numel(),
+         stream())
+    if ev is not None:
+        _probe.end('head_loss', 0.0, ev)
+
+
+def task_loss_weighted_bwd(probs, labels, weights, weight_stride, task_scale, denom, gscale, T, B, dout,
+                           mse_mask: int = 0, prob_form: bool = False) -> None:
+    """``dout`` = gscale a_t w ∂l/∂z / denom_t (``prob_form``: ∂l/∂p), exactly 0 where the weight is 0."""
+    ev = _probe.begin() if _probe is not None else None
+    call('ot_task_loss_weighted_bwd', ptr(probs), ptr(labels), ptr(weights), weight_stride, ptr(task_scale),
+         ptr(denom), ptr(gscale), T, B, mse_mask, int(bool(prob_form)), ptr(dout), stream())
     if ev is not None:
         _probe.end('head_loss', 0.0, ev)
 

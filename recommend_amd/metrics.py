@@ -22,9 +22,39 @@ from typing import Dict
 import numpy as np
 
 
-def auc(labels, scores) -> float:
+def _weighted_auc(y, s, w) -> float:
+    """Σ_{pos i, neg j} w_i w_j ([s_i > s_j] + [s_i == s_j] / 2) / (W_pos W_neg): the Mann-Whitney statistic of the
+    records replicated w times (for integer w exactly that).  Zero-weight records are dropped first, whatever
+    they hold; without weight in one of the classes the result is NaN, as un-weighted."""
+    keep = w > 0
+    y, s, w = y[keep], s[keep], w[keep]
+    pos = y > 0.5
+    wp, wn = np.where(pos, w, 0.0), np.where(pos, 0.0, w)
+    if wp.sum() == 0 or wn.sum() == 0:
+        return float('nan')
+    order = np.argsort(s, kind='mergesort')
+    ss, wp, wn = s[order], wp[order], wn[order]
+    starts = np.concatenate([[0], np.nonzero(np.diff(ss))[0] + 1])            # tie runs
+    gp, gn = np.add.reduceat(wp, starts), np.add.reduceat(wn, starts)
+    below = np.cumsum(gn) - gn                                                # negative weight strictly below the run
+    return float(np.sum(gp * (below + 0.5 * gn)) / (wp.sum() * wn.sum()))
+
+
+def _weights_arg(weights, n: int) -> np.ndarray:
+    w = np.asarray(weights, dtype=np.float64).reshape(-1)
+    if len(w) != n:
+        raise ValueError(f'weights: {n} values expected, got {len(w)}')
+    if not bool(np.all(w >= 0)):
+        raise ValueError('weights must be >= 0 (no NaN)')
+    return w
+
+
+def auc(labels, scores, weights=None) -> float:
+    """``weights`` ([n], >= 0): the weighted statistic (``_weighted_auc``); None: every record counts once."""
     y = np.asarray(labels, dtype=np.float64).reshape(-1)
     s = np.asarray(scores, dtype=np.float64).reshape(-1)
+    if weights is not None:
+        return _weighted_auc(y, s, _weights_arg(weights, len(s)))
     order = np.argsort(s, kind='mergesort')
     ss = s[order]
     n = len(s)
@@ -63,10 +93,22 @@ def roc_trapezoid(tp, fp, P, N) -> float:
     return float(np.sum((fpr[:-1] - fpr[1:]) * (rec[:-1] + rec[1:]) / 2.0))
 
 
-def keras_auc(labels, probs, num_thresholds: int = 200) -> float:
+def keras_auc(labels, probs, num_thresholds: int = 200, weights=None) -> float:
+    """``weights`` ([n], >= 0): Keras's ``sample_weight`` — the true / false positives at each threshold are sums of
+    weights; zero-weight records are dropped first, whatever they hold."""
     thr = keras_thresholds(num_thresholds)
     y = np.asarray(labels).reshape(-1) > 0.5
     p = np.asarray(probs, dtype=np.float64).reshape(-1)
+    if weights is not None:
+        w = _weights_arg(weights, len(p))
+        keep = w > 0
+        y, p, w = y[keep], p[keep], w[keep]
+        order = np.argsort(p, kind='mergesort')
+        ps, ys, ws_ = p[order], y[order], w[order]
+        at = np.searchsorted(ps, thr, side='right')                          # the records > thr are ps[at:]
+        cp = np.concatenate([[0.0], np.cumsum(np.where(ys, ws_, 0.0))])
+        cn = np.concatenate([[0.0], np.cumsum(np.where(ys, 0.0, ws_))])
+        return roc_trapezoid(cp[-1] - cp[at], cn[-1] - cn[at], cp[-1], cn[-1])
     ps = np.sort(p)
     # counts of predictions > thr via searchsorted (O(n log n))
     gt = len(p) - np.searchsorted(ps, thr, side='right')
@@ -137,15 +179,27 @@ class StreamingMetrics:
     ``result`` copies the state to the host once and finalises there in float64.  Both tensors are views of
     one buffer, so a reset is one fill and a read one copy.  On a CPU device the object holds, merges and
     finalises state (``load_state`` / ``all_reduce`` / ``result``); ``update`` needs the GPU (no fallback).
+
+    ``weighted=True`` (Keras metrics under ``sample_weight``): the whole state counts in units of 2^-24
+    of weight — ``update(..., weights=)`` rounds each weight (clamped to [0, 65536]) to the nearest unit and adds that
+    many to its bin, to ``sums[t, 0]`` and, as a factor, to the three sums (``ot_metrics_update_weighted``); a sample
+    of zero units is skipped whatever it holds, and an update without weights adds ``WEIGHT_ONE`` = 2^24 units per
+    sample.  The integers stay exact and commutative, so the state is as reproducible as the un-weighted one, and
+    every reported ratio is the un-weighted formula on it: TP / FP / TN / FN become sums of weights, MSE / MAE /
+    logloss Σ w v / Σ w.  (``sums[t, 0]`` is a double holding an integer: exact while a window's weights sum to
+    less than 2^29.)
     """
 
-    def __init__(self, tasks, device, num_thresholds: int = 200, binary_tasks=None):
+    WEIGHT_ONE = 1 << 24
+
+    def __init__(self, tasks, device, num_thresholds: int = 200, binary_tasks=None, weighted: bool = False):
         import torch
         if binary_tasks is None:
             from .model import BINARY_TASKS as binary_tasks
         self.tasks = list(tasks)
         self.binary = tuple(t in binary_tasks for t in self.tasks)
         self.device = torch.device(device)
+        self.weighted = bool(weighted)
         self.thresholds = keras_thresholds(num_thresholds)
         self.bounds_host = np.unique(np.concatenate([self.thresholds, [0.5]]))        # ascending, 0.5 once
         self.nb = len(self.bounds_host)
@@ -160,10 +214,13 @@ class StreamingMetrics:
         self.sums = self._state[nc:].view(torch.float64).view(T, 4)
         self.bounds = torch.from_numpy(self.bounds_host).to(self.device)
 
-    def update(self, labels, probs) -> None:
-        """``labels``, ``probs``: [T, B] float32 device tensors (rows contiguous).  No host sync."""
+    def update(self, labels, probs, weights=None) -> None:
+        """``labels``, ``probs``: [T, B] float32 device tensors (rows contiguous).  No host sync.
+        ``weights`` (a ``weighted`` object only): [T, B], or [B] / [1, B] for every task, float32 on the device."""
         import torch
         from . import kernels as K
+        if weights is not None and not self.weighted:
+            raise ValueError('StreamingMetrics.update: weights need StreamingMetrics(..., weighted=True)')
         if probs.dim() != 2 or probs.shape[0] != len(self.tasks) or labels.shape != probs.shape:
             raise ValueError(f'StreamingMetrics.update: expected two [{len(self.tasks)}, B] tensors')
         if labels.dtype != torch.float32 or probs.dtype != torch.float32:
@@ -173,6 +230,23 @@ class StreamingMetrics:
         T, B = probs.shape
         if probs.stride(1) != 1 or labels.stride(1) != 1 or (T > 1 and labels.stride(0) != probs.stride(0)):
             labels, probs = labels.contiguous(), probs.contiguous()
+        if self.weighted:
+            if weights is None:
+                weights = torch.ones(B, dtype=torch.float32, device=probs.device)
+            if weights.dtype != torch.float32 or weights.device != probs.device:
+                raise ValueError('StreamingMetrics.update: weights must be float32 on the device of probs')
+            if weights.dim() == 2 and tuple(weights.shape) == (T, B) and T > 1 and weights.stride(0) != 0:
+                weights, wstride = weights.contiguous(), B
+            elif weights.dim() == 2 and tuple(weights.shape) == (T, B) and T > 1:
+                weights, wstride = weights[0].contiguous(), 0                        # one expanded row
+            elif weights.numel() == B:
+                weights, wstride = weights.reshape(-1).contiguous(), 0
+            else:
+                raise ValueError(f'StreamingMetrics.update: weights of shape {tuple(weights.shape)}; expected '
+                                 f'[{T}, {B}] or [{B}]')
+            K.metrics_update_weighted(probs, labels, weights, T, B, probs.stride(0) if T > 1 else B, wstride,
+                                      self.bounds, self.nb, self.counts, self.sums, device=probs.device)
+            return
         K.metrics_update(probs, labels, T, B, probs.stride(0) if T > 1 else B, self.bounds, self.nb, self.counts,
                          self.sums, device=probs.device)
 

@@ -31,7 +31,7 @@ from ._lib import (OT_AX_BF16, OT_AX_BF16_RMSNORM, OT_AX_GELU, OT_AX_RMSNORM, OT
                    OT_EPI_C_BF16, OT_EPI_DROPOUT, OT_EPI_GELU_BWD, OT_EPI_RESIDUAL, OT_EPI_RMSNORM_BWD,
                    OT_EPI_ROW_RSTD, OT_EPI_ROWDOT, OT_GEMM_NN, OT_GEMM_NT, OT_WG_D_BF16, NS_FIELD_BYTES)
 from .config import (OneTransConfig, check_bag_features, check_ns_tokenizer, check_padding_mask, check_pyramid_select,
-                     check_seq_fusion, get_model_config)
+                     check_seq_fusion, check_weighted_loss, get_model_config)
 from .layout import TILE, FlatLayout, RowMap, build_map, head_map, identity_map, layer_maps, round_up
 from .params import init_params, ns_table_offsets
 
@@ -907,6 +907,34 @@ class _BCE(torch.autograd.Function):
         return dprobs, None, None
 
 
+class _WeightedTaskLoss(torch.autograd.Function):
+    """Σ_t a_t (Σ_b w l) / denom_t: the per-element terms of ``_TaskLoss`` (``logits`` given: the
+    gradient goes to the logits) or of ``_BCE`` (``logits`` None: to the probabilities) under per-(task, sample)
+    weights.  The forward leaves the denominators on the device for the backward: no host sync."""
+
+    @staticmethod
+    def forward(ctx, probs, logits, labels, weights, wstride, task_scale, mse_mask, reduction):
+        T, B = probs.shape
+        loss = torch.empty(1, device=probs.device)
+        denom = torch.empty(T, device=probs.device)
+        K.task_loss_weighted_fwd(logits, probs, labels, weights, wstride, task_scale, T, B, loss, denom,
+                                 device=probs.device, mse_mask=mse_mask, reduction=reduction)
+        ctx.save_for_backward(probs, labels, weights, denom, task_scale)
+        ctx.args = (wstride, mse_mask, logits is None)
+        return loss[0]
+
+    @staticmethod
+    def backward(ctx, gl):
+        probs, labels, weights, denom, task_scale = ctx.saved_tensors
+        wstride, mse_mask, prob_form = ctx.args
+        T, B = probs.shape
+        dout = torch.empty_like(probs)
+        gl = gl.reshape(1).contiguous().float()
+        K.task_loss_weighted_bwd(probs, labels, weights, wstride, task_scale, denom, gl, T, B, dout,
+                                 mse_mask=mse_mask, prob_form=prob_form)
+        return (dout, None) + (None,) * 6 if prob_form else (None, dout) + (None,) * 6
+
+
 BINARY_TASKS = ('ctr', 'cvr')      # train.py:83: BCE for these, MSE for every other task
 
 
@@ -917,16 +945,43 @@ def task_mse_mask(tasks) -> int:
     return sum(1 << i for i, t in enumerate(tasks) if t not in BINARY_TASKS)
 
 
-def keras_bce_loss(labels: torch.Tensor, probs: torch.Tensor, tasks=None, label_rank: int = 2) -> torch.Tensor:
+def keras_bce_loss(labels: torch.Tensor, probs: torch.Tensor, tasks=None, label_rank: int = 2, weights=None,
+                   task_scale=None, reduction: str = 'batch') -> torch.Tensor:
     """Sum over tasks of the reference's per-task loss; labels/probs [T, B] device tensors.  ``tasks``
     (names, in row order) selects MSE for tasks other than 'ctr'/'cvr'; None = BCE for every row.
     Probabilities from ``OneTransModel.forward_probs`` carry their heads' logits (``_ot_logits``, as Keras's
     sigmoid output carries ``_keras_logits``) and the BCE is taken from those when the caller's labels were
     [B, 1] (``label_rank`` 2: create_sample_batch, data_loader.py:327).  Keras 2.12 squeezes the [B, 1]
     prediction to [B] for [B] labels (get_tf_dataset's batched scalars, data_loader.py:215-218), which drops
-    the cached logits: ``label_rank`` 1 and probabilities without logits use the clipped probability form."""
+    the cached logits: ``label_rank`` 1 and probabilities without logits use the clipped probability form.
+
+    ``weights`` (float32 device tensor: [T, B], or [B] / [1, B] shared by the tasks; values in [0, 65536], a zero
+    removes the entry whatever its label holds), ``task_scale`` (T coefficients a_t: a sequence or a device tensor)
+    and ``reduction`` ('batch': Σ_t a_t Σ_b w l / B, Keras's SUM_OVER_BATCH_SIZE with ``sample_weight``; 'weights':
+    ... / Σ_b w) select the weighted loss (DESIGN.md §7h).  With ``weights`` None the call is the un-weighted one;
+    ``task_scale`` / ``reduction`` then need weights (pass ones)."""
     mask = task_mse_mask(tasks) if tasks is not None else 0
     z = getattr(probs, '_ot_logits', None) if label_rank >= 2 else None
+    if weights is None and (task_scale is not None or reduction != 'batch'):
+        raise ValueError('keras_bce_loss: task_scale / reduction apply to the weighted loss; pass weights')
+    if weights is not None:
+        T, B = probs.shape
+        if reduction not in _lib.LOSS_REDUCTIONS:
+            raise ValueError(f"unknown reduction {reduction!r}: expected 'batch' or 'weights'")
+        if weights.dtype != torch.float32 or weights.device != probs.device:
+            raise ValueError('keras_bce_loss: weights must be a float32 tensor on the device of probs')
+        if weights.dim() == 2 and tuple(weights.shape) == (T, B) and T > 1:
+            # (an expanded [1, B] row stays one row: weight stride 0)
+            weights, wstride = (weights[0].contiguous(), 0) if weights.stride(0) == 0 else (weights.contiguous(), B)
+        elif weights.numel() == B:
+            weights, wstride = weights.reshape(-1).contiguous(), 0
+        else:
+            raise ValueError(f'keras_bce_loss: weights of shape {tuple(weights.shape)}; expected [{T}, {B}] or [{B}]')
+        if task_scale is not None and not isinstance(task_scale, torch.Tensor):
+            task_scale = torch.tensor([float(a) for a in task_scale], dtype=torch.float32, device=probs.device)
+        if task_scale is not None and (task_scale.numel() != T or task_scale.dtype != torch.float32):
+            raise ValueError(f'keras_bce_loss: task_scale must hold {T} float32 coefficients')
+        return _WeightedTaskLoss.apply(probs, z, labels, weights, wstride, task_scale, mask, reduction)
     if z is not None:
         return _TaskLoss.apply(probs, z, labels, mask)
     return _BCE.apply(probs, labels, mask)
@@ -953,6 +1008,7 @@ class OneTransModel(nn.Module):
         check_seq_fusion(cfg)
         check_bag_features(cfg)
         check_padding_mask(cfg)
+        check_weighted_loss(cfg)
         check_ns_tokenizer(cfg)
         self.padding_mask = bool(getattr(cfg, 'seq_padding_mask', False))
         self.time_fusion = getattr(cfg, 'seq_fusion', 'sep') == 'time'

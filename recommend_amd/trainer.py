@@ -24,8 +24,8 @@ import torch
 
 from . import dist as otdist
 from . import kernels as K
-from .config import OneTransConfig, dense_optimizer_spec, get_model_config
-from .metrics import GroupedAUC, StreamingMetrics, auc, keras_auc
+from .config import LOSS_WEIGHT_MAX, OneTransConfig, dense_optimizer_spec, get_model_config, task_loss_scale
+from .metrics import GroupedAUC, StreamingMetrics, auc, div_no_nan, keras_auc
 from .model import BINARY_TASKS, OneTransModel, keras_bce_loss
 
 
@@ -55,17 +55,64 @@ def _split_batch(batch_data):
     return non_seq, seq, labels, None
 
 
-def label_rank(labels) -> int:
+def label_rank(labels, tasks=None) -> int:
     """Rank of the caller's per-task labels: 1 for [B] (get_tf_dataset's batched scalars), 2 for [B, 1]
-    (create_sample_batch) and for an already stacked [T, B] tensor.  It picks the BCE form (keras_bce_loss)."""
+    (create_sample_batch) and for an already stacked [T, B] tensor.  It picks the BCE form (keras_bce_loss).
+    ``tasks``: look at these keys only (a weighted batch carries weight arrays beside the labels)."""
     if isinstance(labels, torch.Tensor):
         return 2
-    return min(2, max(np.ndim(v) for v in labels.values()))
+    return min(2, max(np.ndim(v) for k, v in labels.items() if tasks is None or k in tasks))
 
 
 def stack_labels(labels: Dict, tasks, dev) -> torch.Tensor:
     """{task: [B,1]} -> [T, B] float32 on device."""
     return torch.stack([torch.as_tensor(labels[t]).reshape(-1).to(dev, torch.float32) for t in tasks])
+
+
+def _weight_row(v, name: str, B: int, dev) -> torch.Tensor:
+    """One weight array ([B] or [B, 1]) as a [B] float32 device tensor.  A host array is checked here (NaN, negative
+    or above the range: ValueError before any launch); a device tensor is never read back (the kernels clamp it)."""
+    if isinstance(v, torch.Tensor) and v.device.type != 'cpu':
+        if not v.is_floating_point():
+            raise ValueError(f'labels[{name!r}]: a floating-point weight expected, got {v.dtype}')
+        t = v
+    else:
+        a = v.numpy() if isinstance(v, torch.Tensor) else np.asarray(v)
+        if a.dtype.kind != 'f':
+            raise ValueError(f'labels[{name!r}]: a floating-point weight expected, got {a.dtype}')
+        if not bool(np.all((a >= 0) & (a <= LOSS_WEIGHT_MAX))):          # (a NaN fails both compares)
+            raise ValueError(f'labels[{name!r}]: weights must lie in [0, {int(LOSS_WEIGHT_MAX)}] (no NaN)')
+        t = torch.from_numpy(np.ascontiguousarray(a))
+    if t.numel() != B or t.dim() > 2 or (t.dim() == 2 and t.shape[1] != 1):
+        raise ValueError(f'labels[{name!r}]: shape {tuple(t.shape)}; expected [{B}] or [{B}, 1]')
+    return t.reshape(-1).to(dev, torch.float32)
+
+
+def stack_weights(labels: Dict, config: OneTransConfig, dev) -> Optional[torch.Tensor]:
+    """The [T, B] float32 weights of a batch, w[t, b] = sample_weight[b] * task_weight_t[b], from
+    ``labels[config.sample_weight_key]`` and ``labels[task + config.label_weight_suffix]`` (each [B] or [B, 1]
+    floating point, a host array or a device tensor; a missing factor is 1), or None when the batch carries
+    neither.  With only a sample weight the result is one row expanded over the tasks (stride 0).  The product of two
+    in-range factors may leave the range: the kernels clamp it."""
+    if isinstance(labels, torch.Tensor):
+        return None
+    tasks = list(config.tasks)
+    sw_key, suf = config.sample_weight_key, config.label_weight_suffix
+    present = [k for k in [sw_key] + [t + suf for t in tasks] if k in labels]
+    if not present:
+        return None
+    B = int(np.prod(np.shape(labels[tasks[0]])))
+    sw = _weight_row(labels[sw_key], sw_key, B, dev) if sw_key in labels else None
+    if all(t + suf not in labels for t in tasks):
+        return sw.unsqueeze(0).expand(len(tasks), B)
+    rows = []
+    for t in tasks:
+        tw = _weight_row(labels[t + suf], t + suf, B, dev) if t + suf in labels else None
+        if tw is None:
+            rows.append(sw if sw is not None else torch.ones(B, dtype=torch.float32, device=dev))
+        else:
+            rows.append(tw * sw if sw is not None else tw)
+    return torch.stack(rows)
 
 
 class OneTransOptimizer:
@@ -406,8 +453,9 @@ class OneTransTrainer:
         weights do not depend on it).  Off by default: the steps then launch exactly what they always did.
         ``group_feature`` (for example ``'user_id'``): the steps also log ``non_seq[group_feature]`` with the batch's
         labels and probabilities (metrics.GroupedAUC), and ``metric_results`` reports ``{t}_uauc*`` as well."""
-        self.train_metrics = StreamingMetrics(self.config.tasks, self.device, num_thresholds)
-        self.val_metrics = StreamingMetrics(self.config.tasks, self.device, num_thresholds)
+        wl = bool(getattr(self.config, 'weighted_loss', False))      # the states then count in weight units
+        self.train_metrics = StreamingMetrics(self.config.tasks, self.device, num_thresholds, weighted=wl)
+        self.val_metrics = StreamingMetrics(self.config.tasks, self.device, num_thresholds, weighted=wl)
         self.group_feature = group_feature
         self.train_grouped = self.val_grouped = None
         if group_feature is not None:
@@ -435,6 +483,42 @@ class OneTransTrainer:
                            f'feature of that name (it has {sorted(non_seq)})')
         return torch.as_tensor(non_seq[self.group_feature]).reshape(-1).to(self.device, torch.int64)
 
+    def _weights(self, labels, grouped) -> Optional[torch.Tensor]:
+        """``stack_weights`` of the batch under ``config.weighted_loss`` (None with the switch off: no key is
+        read).  The grouped AUC stays un-weighted, so a weighted batch while a group feature is logged is refused."""
+        if not getattr(self.config, 'weighted_loss', False):
+            return None
+        w = stack_weights(labels, self.config, self.device)
+        if w is not None and grouped is not None:
+            raise NotImplementedError('weighted_loss with enable_metrics(group_feature=...): the grouped AUC (UAUC) '
+                                      'carries no sample weights; drop the weight keys or the group feature')
+        return w
+
+    def _loss(self, y, probs, labels, w) -> torch.Tensor:
+        if not getattr(self.config, 'weighted_loss', False):
+            # (the rank of the task labels alone: a weight array beside them is inert with the switch off)
+            return keras_bce_loss(y, probs, self.config.tasks, label_rank(labels, self.config.tasks))
+        if w is None:                                    # no weight key in this batch: every weight is 1
+            w = torch.ones(y.shape[1], dtype=torch.float32, device=y.device)
+        scale = task_loss_scale(self.config)
+        if scale is not None:                            # the coefficients as a device tensor, uploaded once
+            cached = getattr(self, '_task_scale', None)
+            if cached is None or cached[0] != scale:
+                cached = self._task_scale = (scale, torch.tensor(scale, dtype=torch.float32, device=y.device))
+            scale = cached[1]
+        return keras_bce_loss(y, probs, self.config.tasks, label_rank(labels, self.config.tasks), weights=w,
+                              task_scale=scale, reduction=self.config.loss_reduction)
+
+    @staticmethod
+    def _update_metrics(metrics: StreamingMetrics, y, probs, w) -> None:
+        if metrics.weighted:
+            metrics.update(y, probs, weights=w)
+        elif w is not None:
+            raise ValueError('the running metrics were created with config.weighted_loss off; call enable_metrics() '
+                             'again after switching it on')
+        else:
+            metrics.update(y, probs)
+
     # --------------------------------------------------------------- steps
     def train_step(self, batch_data, next_batch=None) -> Dict[str, torch.Tensor]:
         """train.py:111-155.  Returns {'total_loss': device scalar} (no host sync).  ``next_batch`` (optional, the
@@ -443,6 +527,7 @@ class OneTransTrainer:
         non_seq, seq, labels, req = _split_batch(batch_data)
         dev = self.device
         y = labels if isinstance(labels, torch.Tensor) else stack_labels(labels, self.config.tasks, dev)
+        w = self._weights(labels, getattr(self, 'train_grouped', None))
         self.model.train()
         if req is not None:      # request-grouped: seq holds one row per request, req the request of each candidate
             probs = self.model.forward_probs_requests(_to_dev(non_seq, dev), _seq_inputs(self.model, seq, dev), req,
@@ -451,13 +536,13 @@ class OneTransTrainer:
             probs = self.model.forward_probs(_to_dev(non_seq, dev), _seq_inputs(self.model, seq, dev), training=True)
         if next_batch is not None and self.model.sharded:
             self.model.route_ahead(_seq_inputs(self.model, next_batch[1], dev))
-        loss = keras_bce_loss(y, probs, self.config.tasks, label_rank(labels))
+        loss = self._loss(y, probs, labels, w)
         self.optimizer.prepare_table_exchange()
         self.optimizer.begin_backward()
         loss.backward()
         self.optimizer.step()
         if self.train_metrics is not None:               # train.py:140-150
-            self.train_metrics.update(y, probs.detach())
+            self._update_metrics(self.train_metrics, y, probs.detach(), w)
         if getattr(self, 'train_grouped', None) is not None:
             self.train_grouped.update(self._group_ids(non_seq), y, probs.detach())
         return {'total_loss': loss.detach(), 'probs': probs.detach()}
@@ -468,14 +553,15 @@ class OneTransTrainer:
         non_seq, seq, labels, req = _split_batch(batch_data)
         dev = self.device
         y = labels if isinstance(labels, torch.Tensor) else stack_labels(labels, self.config.tasks, dev)
+        w = self._weights(labels, getattr(self, 'val_grouped', None))
         if req is not None:
             probs = self.model.forward_probs_requests(_to_dev(non_seq, dev), _seq_inputs(self.model, seq, dev), req,
                                                       training=False)
         else:
             probs = self.model.forward_probs(_to_dev(non_seq, dev), _seq_inputs(self.model, seq, dev), training=False)
-        loss = keras_bce_loss(y, probs, self.config.tasks, label_rank(labels))
+        loss = self._loss(y, probs, labels, w)
         if self.val_metrics is not None:                 # train.py:176-185
-            self.val_metrics.update(y, probs)
+            self._update_metrics(self.val_metrics, y, probs, w)
         if getattr(self, 'val_grouped', None) is not None:
             self.val_grouped.update(self._group_ids(non_seq), y, probs)
         return {'total_loss': loss, 'probs': probs}
@@ -484,21 +570,32 @@ class OneTransTrainer:
         """Per task over a list of batches: 'ctr' / 'cvr' (BCE tasks) the exact rank AUC + the Keras
         200-threshold AUC; any other task (trained with MSE, train.py:88-91) mse and mae, as the
         reference reports for regression tasks (train.py:106, evaluate.py:52-54)."""
-        ps, ys = [], []
+        weighted = bool(getattr(self.config, 'weighted_loss', False))
+        ps, ys, ws = [], [], []
         for b in batches:
             out = self.val_step(b)
             ps.append(out['probs'].cpu().numpy())
             ys.append(stack_labels(b[2], self.config.tasks, 'cpu').numpy())
+            if weighted:
+                w = stack_weights(b[2], self.config, 'cpu')
+                ws.append(np.ones_like(ys[-1]) if w is None else np.clip(np.nan_to_num(w.numpy(), nan=0.0), 0.0,
+                                                                       LOSS_WEIGHT_MAX))
         P, Y = np.concatenate(ps, 1), np.concatenate(ys, 1)
+        W = np.concatenate(ws, 1).astype(np.float64) if weighted else None
         res = {}
         for i, t in enumerate(self.config.tasks):
             if t in BINARY_TASKS:
-                res[f'{t}_auc'] = auc(Y[i], P[i])
-                res[f'{t}_keras_auc'] = keras_auc(Y[i], P[i])
-            else:
+                res[f'{t}_auc'] = auc(Y[i], P[i]) if W is None else auc(Y[i], P[i], weights=W[i])
+                res[f'{t}_keras_auc'] = keras_auc(Y[i], P[i]) if W is None else keras_auc(Y[i], P[i], weights=W[i])
+            elif W is None:
                 e = P[i].astype(np.float64) - Y[i].astype(np.float64)
                 res[f'{t}_mse'] = float(np.mean(e * e))
                 res[f'{t}_mae'] = float(np.mean(np.abs(e)))
+            else:                                        # Σ w v / Σ w over the entries with a weight (div_no_nan)
+                k = W[i] > 0
+                e = P[i][k].astype(np.float64) - Y[i][k].astype(np.float64)
+                res[f'{t}_mse'] = float(div_no_nan(np.sum(W[i][k] * e * e), W[i][k].sum()))
+                res[f'{t}_mae'] = float(div_no_nan(np.sum(W[i][k] * np.abs(e)), W[i][k].sum()))
         return res
 
     def train(self, train_batches, val_batches=None, epochs: int = 1) -> Dict:
