@@ -780,6 +780,22 @@ int ot_sparse_prepare(int E, int64_t num_rows, const int64_t* keys, const float*
                       void* workspace, size_t ws_bytes, void* stream);
 int ot_sparse_finish(float* table, float* accum, int E, int64_t n, float lr, float eps, float clip,
                      const float* sumsq_total, void* workspace, size_t ws_bytes, void* stream);
+/* Row-wise Adagrad (optimizer_config['sparse_optimizer'] = 'rowwise_adagrad'): one accumulator per table row,
+ * accum_rows [num_rows] f32, instead of one per element.  The same de-duplication, fixed summation order and
+ * clip_by_norm as the three forms above, then for every unique valid key r with clipped row g
+ *   accum_rows[r] += (sum_c g[c]^2) / E ;  w[r, c] -= lr g[c] / sqrt(accum_rows[r] + eps).
+ * The row's sum of squares is added in an order fixed by E alone (no atomics), the same in the three forms: with
+ * the clip off they give the same bits, run to run and form to form.  A row no valid key names (dense form: a row
+ * whose clipped gradient is all zeros) keeps its weight and accumulator bits.  E: a multiple of 4, <= 1024, in all
+ * three.  Workspaces as for the element-wise forms (ot_sparse_adagrad_workspace_size: one call and finish, after
+ * the unchanged ot_sparse_prepare; ot_dense_adagrad_workspace_size: dense). */
+int ot_sparse_adagrad_rowwise(float* table, float* accum_rows, int E, int64_t num_rows, const int64_t* keys,
+                              const float* grads, int64_t n, float lr, float eps, float clip, void* workspace,
+                              size_t ws_bytes, void* stream);
+int ot_dense_adagrad_rowwise(float* table, float* accum_rows, const float* grad, int64_t num_rows, int E, float lr,
+                             float eps, float clip, void* workspace, size_t ws_bytes, void* stream);
+int ot_sparse_finish_rowwise(float* table, float* accum_rows, int E, int64_t n, float lr, float eps, float clip,
+                             const float* sumsq_total, void* workspace, size_t ws_bytes, void* stream);
 
 /* ---- row-sharded embedding tables (shard.hip) ------------------------------
  * Row id lives on rank id % world at local row id / world.  ot_shard_route buckets n ids by owner

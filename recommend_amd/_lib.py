@@ -208,6 +208,9 @@ SIGNATURES = {
     'ot_dense_adagrad': (c_int, [P, P, P, I64, c_int, c_float, c_float, c_float, P, c_size_t, P]),
     'ot_sparse_prepare': (c_int, [c_int, I64, P, P, I64, P, P, c_size_t, P]),
     'ot_sparse_finish': (c_int, [P, P, c_int, I64, c_float, c_float, c_float, P, P, c_size_t, P]),
+    'ot_sparse_adagrad_rowwise': (c_int, [P, P, c_int, I64, P, P, I64, c_float, c_float, c_float, P, c_size_t, P]),
+    'ot_dense_adagrad_rowwise': (c_int, [P, P, P, I64, c_int, c_float, c_float, c_float, P, c_size_t, P]),
+    'ot_sparse_finish_rowwise': (c_int, [P, P, c_int, I64, c_float, c_float, c_float, P, P, c_size_t, P]),
     'ot_shard_route_workspace_size': (c_size_t, [I64]),
     'ot_shard_route': (c_int, [P, I64, I64, c_int, P, P, P, P, c_size_t, P]),
     'ot_shard_route_unique_workspace_size': (c_size_t, [I64]),

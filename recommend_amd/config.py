@@ -297,6 +297,27 @@ def dense_optimizer_spec(config: OneTransConfig) -> Tuple[str, Dict[str, float]]
     return 'adam', {'lr': lr, 'beta1': 0.9, 'beta2': 0.999, 'eps': 1e-7}
 
 
+SPARSE_OPTIMIZERS = ('adagrad', 'rowwise_adagrad')
+
+
+def sparse_optimizer_spec(config: OneTransConfig) -> Tuple[str, Dict[str, float]]:
+    """The embedding-table optimizer ``optimizer_config['sparse_optimizer']`` selects: ``(kind, params)`` with
+    params ``{lr, eps, initial_accumulator, clip}`` (``optimizer_config['sparse_lr']``, ``adagrad_epsilon``,
+    ``adagrad_initial_accumulator``, ``sparse_clip_norm``).
+
+    * ``'adagrad'`` (the default, also without the key): element-wise Keras Adagrad, one accumulator per element.
+    * ``'rowwise_adagrad'``: one accumulator per table row, ``A[r] += mean_c g[r, c]^2``.
+    * any other name: ValueError.  (Unlike the dense side, where the reference itself falls back to Adam, the
+      reference never reads this key: there is no fallback to mirror, and a name that is silently ignored is a bug.)"""
+    oc = config.optimizer_config
+    name = oc.get('sparse_optimizer', 'adagrad')
+    if name not in SPARSE_OPTIMIZERS:
+        raise ValueError(f'unknown sparse_optimizer {name!r}: expected one of {list(SPARSE_OPTIMIZERS)}')
+    return name, {'lr': float(oc.get('sparse_lr', 0.1)), 'eps': float(config.adagrad_epsilon),
+                  'initial_accumulator': float(config.adagrad_initial_accumulator),
+                  'clip': float(config.sparse_clip_norm)}
+
+
 DEFAULT_CONFIG = OneTransConfig()
 
 # ---------------------------------------------------------------------------
@@ -559,6 +580,6 @@ def algorithmic_flops_per_sample(cfg: OneTransConfig, seq_lens: List[int], f_ns:
 
 
 __all__ = ['OneTransConfig', 'OneTransSmallConfig', 'OneTransLargeConfig', 'get_model_config',
-           'dense_optimizer_spec', 'DEFAULT_CONFIG', 'workload_config', 'algorithmic_flops_per_sample',
+           'dense_optimizer_spec', 'sparse_optimizer_spec', 'SPARSE_OPTIMIZERS', 'DEFAULT_CONFIG', 'workload_config', 'algorithmic_flops_per_sample',
            'CRITEO_CARDINALITIES', 'check_bag_features', 'check_ns_tokenizer', 'even_ns_groups', 'ns_group_layout',
            'ns_group_mode']

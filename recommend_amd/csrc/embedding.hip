@@ -9,6 +9,8 @@
 //   4. clip_by_norm(clip) over the unique-row gradient (one device scalar, no host sync)
 //   5. acc[r] += g^2 ; w[r] -= lr * g / sqrt(acc[r] + eps)
 // HBM-bound: the row reads in step 3 and the table/accumulator row RMW in step 5.
+// Row-wise Adagrad (the *_rowwise entry points) shares steps 1-4 and replaces step 5 by
+//   5'. acc[r] += (sum_c g[r, c]^2) / E ; w[r, c] -= lr * g[r, c] / sqrt(acc[r] + eps), acc one float per row
 #include "keyed.h"
 
 namespace ot {
@@ -199,6 +201,108 @@ __global__ void clip_from_sumsq_kernel(const float* __restrict__ sumsq, float cl
   }
 }
 
+// ---- row-wise Adagrad: one accumulator per table row --------------------------------------------------------
+//   A[r] += (sum_c g[c]^2) / E ;  W[r, c] -= lr g[c] / sqrt(A[r] + eps)
+// A row is worked by tps = tps_for(E) threads, group threadIdx.x / tps of a 256-thread block, as in the kernels
+// above; lane lt keeps the row's columns 4 (lt + k tps) .. + 3 of pass k in registers (E <= 1024: at most
+// ROW_PASSES passes), so the gradient is read once.
+constexpr int ROW_PASSES = 4;
+
+// Sum of squares of one row, the same bits in every thread of the row.  The order is fixed by E alone: a lane adds
+// x^2, y^2, z^2, w^2 of its passes in pass order (fmaf chain), the lanes' sums meet in LDS and are added in lane
+// order.  No shuffles: when tps is no power of two (E = 12, 20, 24, 40, ...) a row's lanes straddle a wavefront
+// boundary.  Every thread of the block calls it (one barrier inside); a thread of no row passes zeros.  The caller
+// puts a barrier before the next call (part is read until then).
+__device__ __forceinline__ float row_sumsq(const f32x4 (&g)[ROW_PASSES], int tps, float (&part)[256]) {
+  float q = 0.f;
+#pragma unroll
+  for (int k = 0; k < ROW_PASSES; ++k) {
+    const f32x4 v = g[k];
+    q = fmaf(v.w, v.w, fmaf(v.z, v.z, fmaf(v.y, v.y, fmaf(v.x, v.x, q))));
+  }
+  part[threadIdx.x] = q;
+  __syncthreads();
+  const int first = threadIdx.x / tps * tps;
+  if (first + tps > 256) return 0.f;              // the threads past the block's last whole group
+  float s = 0.f;
+  for (int j = 0; j < tps; ++j) s += part[first + j];
+  return s;
+}
+
+// One row's update by its tps threads (active: this thread has a row; all 256 threads call).  g = the row's
+// gradient before the clip scale sc.  The accumulator is read by every lane before row_sumsq's barrier and written
+// by lane 0 after it, so no lane can read the new value.  A lane whose four gradients are all zero leaves its
+// weights alone, and a row whose sum is zero its accumulator (A + 0 and w - 0 are the same bits): the dense form
+// then writes nothing to the rows no key named.
+__device__ __forceinline__ void rowwise_update(float* w, float* a, const float* __restrict__ g, int E, float sc,
+                                               int tps, int lt, bool active, float lr, float eps,
+                                               float (&part)[256]) {
+  f32x4 gv[ROW_PASSES];
+  float a_old = 0.f;
+#pragma unroll
+  for (int k = 0; k < ROW_PASSES; ++k) {
+    const int c = (lt + k * tps) * 4;
+    gv[k] = f32x4{0.f, 0.f, 0.f, 0.f};
+    if (active && c < E) gv[k] = *reinterpret_cast<const f32x4*>(g + c) * sc;
+  }
+  if (active) a_old = a[0];
+  const float ssq = row_sumsq(gv, tps, part);
+  if (!active) return;
+  const float a_new = a_old + ssq / (float)E;
+  const float den = sqrtf(a_new + eps);
+  if (lt == 0 && ssq != 0.f) a[0] = a_new;
+#pragma unroll
+  for (int k = 0; k < ROW_PASSES; ++k) {
+    const int c = (lt + k * tps) * 4;
+    const f32x4 v = gv[k];
+    if (c >= E || (v.x == 0.f && v.y == 0.f && v.z == 0.f && v.w == 0.f)) continue;
+    f32x4 wv = *reinterpret_cast<const f32x4*>(w + c);
+    wv.x -= lr * v.x / den;
+    wv.y -= lr * v.y / den;
+    wv.z -= lr * v.z / den;
+    wv.w -= lr * v.w / den;
+    *reinterpret_cast<f32x4*>(w + c) = wv;
+  }
+}
+
+__global__ __launch_bounds__(256) void rowwise_apply_kernel(float* table, float* accum_rows, int E,
+                                                            const uint32_t* __restrict__ ksorted,
+                                                            const int32_t* __restrict__ seg_start,
+                                                            const int32_t* __restrict__ nuniq,
+                                                            const float* __restrict__ gsum,
+                                                            const float* __restrict__ scale, int tps, float lr,
+                                                            float eps) {
+  __shared__ float part[256];
+  const int spb = 256 / tps;
+  const int ls = threadIdx.x / tps;
+  const int64_t s = (int64_t)blockIdx.x * spb + ls;
+  const int lt = threadIdx.x % tps;
+  uint32_t key = 0xFFFFFFFFu;
+  if (ls < spb && s < nuniq[0]) key = ksorted[seg_start[s]];
+  const bool active = key != 0xFFFFFFFFu;
+  const int64_t r = active ? (int64_t)key : 0, sr = active ? s : 0;
+  rowwise_update(table + r * E, accum_rows + r, gsum + sr * E, E, scale[0], tps, lt, active, lr, eps, part);
+}
+
+// The dense form: every row of the table against the all-reduced [num_rows, E] gradient, 256 / tps rows per block
+// and pass of the grid-stride loop (the same row-to-threads mapping as above, hence the same bits).
+__global__ __launch_bounds__(256) void dense_rowwise_kernel(float* table, float* accum_rows,
+                                                            const float* __restrict__ g, int64_t num_rows, int E,
+                                                            const float* __restrict__ scale, int tps, float lr,
+                                                            float eps) {
+  __shared__ float part[256];
+  const int rpb = 256 / tps;
+  const int ls = threadIdx.x / tps;
+  const int lt = threadIdx.x % tps;
+  const float sc = scale[0];
+  for (int64_t base = (int64_t)blockIdx.x * rpb; base < num_rows; base += (int64_t)gridDim.x * rpb) {
+    const bool active = ls < rpb && base + ls < num_rows;
+    const int64_t r = active ? base + ls : 0;
+    rowwise_update(table + r * E, accum_rows + r, g + r * E, E, sc, tps, lt, active, lr, eps, part);
+    __syncthreads();                               // part is written again in the next pass
+  }
+}
+
 struct SparseWs {
   uint32_t *k_in, *k_out;
   int32_t *v_in, *v_out, *flags, *pos, *seg_start, *nuniq, *pcount, *pstart;
@@ -371,4 +475,69 @@ extern "C" int ot_sparse_finish(float* table, float* accum, int E, int64_t n, fl
                      w.gsum, w.scale, tps, lr, eps);
   OT_LAUNCH_CHECK("ot_sparse_finish(apply)");
   return OT_OK;
+}
+
+// ---- row-wise Adagrad entry points: the three forms above with one accumulator per table row ----------------
+static int launch_rowwise_apply(const SparseWs& w, float* table, float* accum_rows, int E, int64_t n, float lr,
+                                float eps, hipStream_t s, const char* label) {
+  const int tps = tps_for(E);
+  hipLaunchKernelGGL(rowwise_apply_kernel, dim3(ceil_div(n, 256 / tps)), dim3(256), 0, s, table, accum_rows, E,
+                     w.k_out, w.seg_start, w.nuniq, w.gsum, w.scale, tps, lr, eps);
+  OT_LAUNCH_CHECK(label);
+  return OT_OK;
+}
+
+extern "C" int ot_sparse_adagrad_rowwise(float* table, float* accum_rows, int E, int64_t num_rows,
+                                         const int64_t* keys, const float* grads, int64_t n, float lr, float eps,
+                                         float clip, void* workspace, size_t ws_bytes, void* stream) {
+  OT_REQUIRE(table && accum_rows && keys && grads, "ot_sparse_adagrad_rowwise: null operand");
+  OT_REQUIRE(E > 0 && E % 4 == 0 && E <= 1024, "ot_sparse_adagrad_rowwise: E=%d must be a multiple of 4 <= 1024", E);
+  OT_REQUIRE(num_rows > 0 && num_rows < 0xFFFFFFFFLL, "ot_sparse_adagrad_rowwise: num_rows out of range");
+  OT_REQUIRE(n >= 0 && n < 2147483647LL, "ot_sparse_adagrad_rowwise: n out of range");
+  if (n == 0) return OT_OK;
+  SparseWs w = carve(workspace, n, E);
+  OT_REQUIRE(ws_bytes >= w.total, "ot_sparse_adagrad_rowwise: workspace too small (%zu < %zu)", ws_bytes, w.total);
+  hipStream_t s = (hipStream_t)stream;
+  OT_TRY(segment_rows(w, E, num_rows, keys, grads, n, s));
+  const unsigned g2 = ceil_div(n, 256 / tps_for(E));
+  hipLaunchKernelGGL(clip_scale_kernel, dim3(1), dim3(256), 0, s, w.sq_part, (int)g2, clip, w.scale);
+  OT_LAUNCH_CHECK("ot_sparse_adagrad_rowwise(clip)");
+  return launch_rowwise_apply(w, table, accum_rows, E, n, lr, eps, s, "ot_sparse_adagrad_rowwise(apply)");
+}
+
+extern "C" int ot_dense_adagrad_rowwise(float* table, float* accum_rows, const float* grad, int64_t num_rows, int E,
+                                        float lr, float eps, float clip, void* workspace, size_t ws_bytes,
+                                        void* stream) {
+  OT_REQUIRE(table && accum_rows && grad && workspace, "ot_dense_adagrad_rowwise: null operand");
+  OT_REQUIRE(E > 0 && E % 4 == 0 && E <= 1024, "ot_dense_adagrad_rowwise: E=%d must be a multiple of 4 <= 1024", E);
+  OT_REQUIRE(ws_bytes >= ot_dense_adagrad_workspace_size(), "ot_dense_adagrad_rowwise: workspace too small");
+  if (num_rows <= 0) return OT_OK;
+  hipStream_t s = (hipStream_t)stream;
+  const int64_t n4 = num_rows * E / 4;
+  float* part = (float*)workspace;
+  float* scale = part + DENSE_GRID;
+  hipLaunchKernelGGL(dense_sumsq_kernel, dim3(DENSE_GRID), dim3(256), 0, s, grad, n4, part);
+  OT_LAUNCH_CHECK("ot_dense_adagrad_rowwise(norm)");
+  hipLaunchKernelGGL(clip_scale_kernel, dim3(1), dim3(256), 0, s, part, DENSE_GRID, clip, scale);
+  OT_LAUNCH_CHECK("ot_dense_adagrad_rowwise(clip)");
+  const int tps = tps_for(E);
+  const unsigned grid = std::min<int64_t>(DENSE_GRID, ceil_div(num_rows, 256 / tps));
+  hipLaunchKernelGGL(dense_rowwise_kernel, dim3(grid), dim3(256), 0, s, table, accum_rows, grad, num_rows, E, scale,
+                     tps, lr, eps);
+  OT_LAUNCH_CHECK("ot_dense_adagrad_rowwise(apply)");
+  return OT_OK;
+}
+
+extern "C" int ot_sparse_finish_rowwise(float* table, float* accum_rows, int E, int64_t n, float lr, float eps,
+                                        float clip, const float* sumsq_total, void* workspace, size_t ws_bytes,
+                                        void* stream) {
+  OT_REQUIRE(table && accum_rows && sumsq_total && workspace, "ot_sparse_finish_rowwise: null operand");
+  OT_REQUIRE(E > 0 && E % 4 == 0 && E <= 1024, "ot_sparse_finish_rowwise: E=%d must be a multiple of 4 <= 1024", E);
+  if (n <= 0) return OT_OK;
+  SparseWs w = carve(workspace, n, E);
+  OT_REQUIRE(ws_bytes >= w.total, "ot_sparse_finish_rowwise: workspace too small (%zu < %zu)", ws_bytes, w.total);
+  hipStream_t s = (hipStream_t)stream;
+  hipLaunchKernelGGL(clip_from_sumsq_kernel, dim3(1), dim3(64), 0, s, sumsq_total, clip, w.scale);
+  OT_LAUNCH_CHECK("ot_sparse_finish_rowwise(clip)");
+  return launch_rowwise_apply(w, table, accum_rows, E, n, lr, eps, s, "ot_sparse_finish_rowwise(apply)");
 }

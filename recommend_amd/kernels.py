@@ -1074,6 +1074,32 @@ def sparse_finish(table, accum, E, n, lr, eps, clip, sumsq_total, ws) -> None:
          ptr(ws), ws.numel(), stream())
 
 
+def sparse_adagrad_rowwise(table, accum_rows, E, num_rows, keys, grads, n, lr, eps, clip, device=None) -> None:
+    """Row-wise Adagrad (``accum_rows`` [num_rows]): the one-call form."""
+    ws = workspace(size('ot_sparse_adagrad_workspace_size', n, E), device)
+    ev = _probe.begin() if _probe is not None else None
+    call('ot_sparse_adagrad_rowwise', ptr(table), ptr(accum_rows), E, num_rows, ptr(keys), ptr(grads), n, float(lr),
+         float(eps), float(clip), ptr(ws), ws.numel(), stream())
+    if ev is not None:
+        _probe.end('embedding', 0.0, ev)
+
+
+def dense_adagrad_rowwise(table, accum_rows, grad, num_rows, E, lr, eps, clip, device=None) -> None:
+    """Row-wise Adagrad over a dense [num_rows, E] gradient (the data-parallel form)."""
+    ws = workspace(size('ot_dense_adagrad_workspace_size'), device)
+    ev = _probe.begin() if _probe is not None else None
+    call('ot_dense_adagrad_rowwise', ptr(table), ptr(accum_rows), ptr(grad), num_rows, E, float(lr), float(eps),
+         float(clip), ptr(ws), ws.numel(), stream())
+    if ev is not None:
+        _probe.end('embedding', 0.0, ev)
+
+
+def sparse_finish_rowwise(table, accum_rows, E, n, lr, eps, clip, sumsq_total, ws) -> None:
+    """Row-wise Adagrad: the second phase after ``sparse_prepare`` (row-sharded tables)."""
+    call('ot_sparse_finish_rowwise', ptr(table), ptr(accum_rows), E, n, float(lr), float(eps), float(clip),
+         ptr(sumsq_total), ptr(ws), ws.numel(), stream())
+
+
 def sparse_workspace(n, E, device):
     return workspace(size('ot_sparse_adagrad_workspace_size', n, E), device)
 

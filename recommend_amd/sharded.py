@@ -14,7 +14,8 @@ transformer stays data-parallel; only the table is partitioned:
   order) and travel the same routes to their owners (all-to-all), are scaled by 1/world (each
   rank's loss is a mean over its local batch), de-duplicated across ranks, and applied with the
   sparse Keras Adagrad; the per-table ``clip_by_norm`` uses the global norm (an all-reduce of each
-  owner's squared norm between ``ot_sparse_prepare`` and ``ot_sparse_finish``).
+  owner's squared norm between ``ot_sparse_prepare`` and ``ot_sparse_finish``; under row-wise Adagrad,
+  ``apply_gradient(kind='rowwise_adagrad')``, ``ot_sparse_finish_rowwise`` and one accumulator per shard row).
 
 All bytes move on device; the only host traffic is the ``world`` split sizes the all-to-alls need.  That
 one host wait is taken off the main stream: the ids are staged, routed and their per-owner counts
@@ -212,9 +213,15 @@ class ShardedTable:
         return out
 
     def apply_gradient(self, route, grads: torch.Tensor, accum: torch.Tensor, lr: float, eps: float,
-                       clip: float) -> None:
+                       clip: float, kind: str = 'adagrad') -> None:
         """Sparse Adagrad on the owners for ``grads`` (rows in the order of the ids of the ``lookup``
-        that produced ``route`` = its ``last_route``)."""
+        that produced ``route`` = its ``last_route``).  ``kind``: 'adagrad' (``accum`` shaped like the shard) or
+        'rowwise_adagrad' (``accum`` [rows_alloc], one entry per shard row)."""
+        if kind not in ('adagrad', 'rowwise_adagrad'):
+            raise ValueError(f'{self.name}: unknown sparse optimizer {kind!r}')
+        want = (self.rows_alloc,) if kind == 'rowwise_adagrad' else (self.rows_alloc, self.E)
+        if tuple(accum.shape) != want:
+            raise ValueError(f'{self.name}: accumulator of shape {tuple(accum.shape)} for {kind!r}, expected {want}')
         if route is None:
             raise RuntimeError(f'{self.name}: apply_gradient without a lookup route')
         n, perm, send_splits, recv_splits, recv_local, R = route
@@ -244,14 +251,18 @@ class ShardedTable:
                 sumsq.copy_(h)
             else:
                 dist.all_reduce(sumsq)
-        K.sparse_finish(self.table, accum, E, R, lr, eps, clip, sumsq, ws)
+        finish = K.sparse_finish_rowwise if kind == 'rowwise_adagrad' else K.sparse_finish
+        finish(self.table, accum, E, R, lr, eps, clip, sumsq, ws)
         if ev0 is not None:
             self.events.append((ev0, self._mark()))
 
     def full_table(self, shard: Optional[torch.Tensor] = None) -> torch.Tensor:
         """Gather the logical table on every rank (tests / checkpoints of small tables); ``shard``: another
-        tensor laid out like this rank's shard (the table's Adagrad accumulator) to gather instead."""
+        tensor laid out like this rank's shard to gather instead: the table's Adagrad accumulator, [rows_alloc, E] or,
+        per row, [rows_alloc] (the result is then [num_rows])."""
         shard = self.table if shard is None else shard
+        if shard.shape[0] != self.rows_alloc:
+            raise ValueError(f'{self.name}: a shard of {shard.shape[0]} rows, expected {self.rows_alloc}')
         if self.world == 1:
             return shard[:self.local_rows].clone()
         gloo = dist.get_backend() == 'gloo'
@@ -259,7 +270,7 @@ class ShardedTable:
         parts = [torch.empty_like(src) for _ in range(self.world)]
         dist.all_gather(parts, src)
         parts = [q.to(self.device) for q in parts]
-        out = torch.empty(self.num_rows, self.E, device=self.device)
+        out = torch.empty((self.num_rows,) + tuple(shard.shape[1:]), dtype=shard.dtype, device=self.device)
         for r in range(self.world):
             lr_ = (self.num_rows - r + self.world - 1) // self.world
             out[r::self.world] = parts[r][:lr_]

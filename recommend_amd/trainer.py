@@ -4,7 +4,8 @@
 convention, train.py:118) -> Σ_task Keras BCE (train.py:124-128) -> backward (train.py:131) ->
 per-variable clip_by_norm (train.py:134-135) -> RMSprop(momentum) or Adam, whichever
 ``optimizer_config['dense_optimizer']`` selects (train.py:53-76, 138) -> sparse Adagrad
-on the embedding rows touched (build extension).  Defect D5 mapping: the trainer reads
+on the embedding rows touched (build extension), with one accumulator per element or, under
+``optimizer_config['sparse_optimizer'] = 'rowwise_adagrad'``, per row.  Defect D5 mapping: the trainer reads
 ``gradient_clip_norm`` (the reference reads the absent ``gradient_clip``) and
 ``optimizer_config['dense_lr']`` (the reference reads the absent ``learning_rate``); mixed
 precision is not enabled (the reference reads the absent ``system_config``) — the HIP path
@@ -24,7 +25,8 @@ import torch
 
 from . import dist as otdist
 from . import kernels as K
-from .config import LOSS_WEIGHT_MAX, OneTransConfig, dense_optimizer_spec, get_model_config, task_loss_scale
+from .config import (LOSS_WEIGHT_MAX, OneTransConfig, dense_optimizer_spec, get_model_config, sparse_optimizer_spec,
+                     task_loss_scale)
 from .metrics import GroupedAUC, StreamingMetrics, auc, div_no_nan, keras_auc
 from .model import BINARY_TASKS, OneTransModel, keras_bce_loss
 
@@ -119,8 +121,11 @@ class OneTransOptimizer:
     """Dense: clip_by_norm per reference variable + the optimizer ``optimizer_config['dense_optimizer']`` names
     (config.dense_optimizer_spec, train.py:53-76) on the flat buffer, one fused multi-segment call: Keras
     RMSprop(momentum) (ot_clip_rmsprop) or Keras Adam (ot_clip_adam).  Both keep two flat state buffers: ``v`` and
-    ``m`` (RMSprop: mean square and momentum; Adam: second and first moment).  Sparse: Keras Adagrad on the
-    de-duplicated rows of each embedding table (ot_sparse_adagrad)."""
+    ``m`` (RMSprop: mean square and momentum; Adam: second and first moment).  Sparse: the optimizer
+    ``optimizer_config['sparse_optimizer']`` names (config.sparse_optimizer_spec) on the de-duplicated rows of each
+    embedding table: Keras Adagrad with one accumulator per element (``'adagrad'``, ot_sparse_adagrad; ``acc[name]``
+    is shaped like the table) or per row (``'rowwise_adagrad'``, ot_sparse_adagrad_rowwise; ``acc[name]`` is [rows],
+    for a row-sharded table one entry per allocated shard row)."""
 
     def __init__(self, model: OneTransModel, config: OneTransConfig):
         self.model = model
@@ -137,15 +142,18 @@ class OneTransOptimizer:
         else:
             self.beta1, self.beta2 = spec['beta1'], spec['beta2']
         self.clip = float(config.gradient_clip_norm)
-        self.sparse_lr = float(oc.get('sparse_lr', 0.1))
-        self.sparse_eps = float(config.adagrad_epsilon)
-        self.sparse_clip = float(config.sparse_clip_norm)
+        self.sparse_kind, sspec = sparse_optimizer_spec(config)      # (an unknown name: ValueError)
+        self.sparse_lr, self.sparse_eps, self.sparse_clip = sspec['lr'], sspec['eps'], sspec['clip']
         dev = model.flat.device
         self.v = torch.zeros_like(model.flat.data)
         self.m = torch.zeros_like(model.flat.data)
         self.segs = torch.from_numpy(model.layout.segments.reshape(-1)).to(dev)
         self.nseg = model.layout.segments.shape[0]
-        self.acc = {k: torch.full_like(t, float(config.adagrad_initial_accumulator)) for k, t in model.tables.items()}
+        if self.sparse_kind == 'rowwise_adagrad':
+            self.acc = {k: torch.full((t.shape[0],), sspec['initial_accumulator'], dtype=torch.float32,
+                                      device=t.device) for k, t in model.tables.items()}
+        else:
+            self.acc = {k: torch.full_like(t, sspec['initial_accumulator']) for k, t in model.tables.items()}
         # data-parallel exchange of replicated tables: dense all-reduce up to this size, else all-gather
         self.dense_exchange_bytes = int(float(os.environ.get('ONETRANS_DENSE_EXCHANGE_MB', '512')) * 2 ** 20)
         # ... and of those, all-reduce only the rows some rank touched (the union, from a 1-byte-per-row
@@ -171,10 +179,15 @@ class OneTransOptimizer:
     def state_dict(self) -> Dict[str, np.ndarray]:
         """Host copies of what a resumed run needs besides the weights: the dense kind, ``steps_done`` (Adam's bias
         correction and the warm-up ramp), the two flat dense slots and every table's Adagrad accumulator
-        (``acc.<table>``).  Like ``OneTransModel.param_dict``, a COLLECTIVE with a row-sharded table (its
-        accumulator is all-gathered into the logical table's row order): every rank calls it."""
+        (``acc.<table>``: shaped like the table, or [rows] under ``'rowwise_adagrad'``).  ``'sparse_kind'`` names
+        the table optimizer when it is not ``'adagrad'``: an ``'adagrad'`` state keeps the keys it always had, and a
+        state without the key is an ``'adagrad'`` one.  Like ``OneTransModel.param_dict``, a COLLECTIVE with a
+        row-sharded table (its accumulator is all-gathered into the logical table's row order): every rank calls
+        it."""
         out = {'dense_kind': np.array(self.kind), 'steps_done': np.array(self.steps_done, dtype=np.int64),
                'dense.v': self.v.detach().cpu().numpy().copy(), 'dense.m': self.m.detach().cpu().numpy().copy()}
+        if self.sparse_kind != 'adagrad':
+            out['sparse_kind'] = np.array(self.sparse_kind)
         for name, a in self.acc.items():
             sh = self.model.sharded.get(name)
             src = sh.full_table(a) if sh is not None else a
@@ -183,11 +196,16 @@ class OneTransOptimizer:
 
     def load_state_dict(self, d: Dict[str, np.ndarray]) -> None:
         """Restore ``state_dict()``'s arrays.  Everything is checked before anything is written: a state of the
-        other dense kind, a missing entry or a shape that does not fit raises ValueError and leaves the optimizer
-        as it was.  A row-sharded table's accumulator keeps this rank's rows (id % world == rank)."""
+        other dense or sparse kind (a state without ``'sparse_kind'``, written before there was a choice, counts as
+        ``'adagrad'``), a missing entry or a shape that does not fit raises ValueError and leaves the optimizer as
+        it was.  A row-sharded table's accumulator keeps this rank's rows (id % world == rank)."""
         kind = str(np.asarray(d['dense_kind']))
         if kind != self.kind:
             raise ValueError(f'optimizer state is for dense optimizer {kind!r}, this optimizer runs {self.kind!r}')
+        skind = str(np.asarray(d['sparse_kind'])) if 'sparse_kind' in d else 'adagrad'
+        if skind != self.sparse_kind:
+            raise ValueError(f'optimizer state is for sparse optimizer {skind!r}, this optimizer runs '
+                             f'{self.sparse_kind!r}')
         todo = []
         for key, dst in (('dense.v', self.v), ('dense.m', self.m)):
             todo.append((key, dst, np.asarray(d[key]) if key in d else None))
@@ -196,8 +214,9 @@ class OneTransOptimizer:
             arr = np.asarray(d[key]) if key in d else None
             sh = self.model.sharded.get(name)
             if sh is not None:
-                if arr is not None and arr.shape != (sh.num_rows, sh.E):
-                    raise ValueError(f'{key}: stored shape {arr.shape} != ({sh.num_rows}, {sh.E})')
+                full = (sh.num_rows,) if self.sparse_kind == 'rowwise_adagrad' else (sh.num_rows, sh.E)
+                if arr is not None and arr.shape != full:
+                    raise ValueError(f'{key}: stored shape {arr.shape} != {full}')
                 todo.append((key, a[:sh.local_rows], None if arr is None else arr[sh.rank::sh.world]))
             else:
                 todo.append((key, a, arr))
@@ -209,6 +228,11 @@ class OneTransOptimizer:
         for key, dst, arr in todo:
             dst.copy_(torch.as_tensor(np.ascontiguousarray(arr), dtype=torch.float32))
         self.steps_done = int(np.asarray(d['steps_done']))
+
+    def state_nbytes(self) -> int:
+        """Device bytes of the optimizer state on this rank: the two flat dense slots plus every table's
+        accumulator (a row-sharded table: this rank's shard)."""
+        return sum(t.numel() * t.element_size() for t in (self.v, self.m, *self.acc.values()))
 
     def _mark(self):
         if self.exchange_events is None:
@@ -401,13 +425,14 @@ class OneTransOptimizer:
                         self.current_lr(), self.beta1, self.beta2, self.eps, self.steps_done, self.clip,
                         device=m.flat.device)
         m.refresh_shadow()
+        rowwise = self.sparse_kind == 'rowwise_adagrad'
         for (name, keys, grads) in m._pending_sparse:
             table = m.tables[name]
             rows, E = table.shape
             if name in m.sharded:
                 # row-sharded: gradient rows go to their owners (all-to-all), global-norm clip, Adagrad
                 m.sharded[name].apply_gradient(keys, grads, self.acc[name], self.sparse_lr, self.sparse_eps,
-                                               self.sparse_clip)
+                                               self.sparse_clip, kind=self.sparse_kind)
             elif name in early:
                 # one all-reduce of the de-duplicated dense gradient (started above) instead of
                 # all-gathering every rank's rows
@@ -419,12 +444,14 @@ class OneTransOptimizer:
                 if idx is not None:                      # the union's summed rows back into the dense gradient
                     g.index_copy_(0, idx, cg)
                 g.mul_(1.0 / otdist.world())
-                K.dense_adagrad(table, self.acc[name], g, rows, E, self.sparse_lr, self.sparse_eps,
-                                self.sparse_clip, device=table.device)
+                dense_update = K.dense_adagrad_rowwise if rowwise else K.dense_adagrad
+                dense_update(table, self.acc[name], g, rows, E, self.sparse_lr, self.sparse_eps, self.sparse_clip,
+                             device=table.device)
             else:
                 keys, grads = otdist.allgather_sparse(keys, grads)
-                K.sparse_adagrad(table, self.acc[name], E, rows, keys, grads, keys.numel(),
-                                 self.sparse_lr, self.sparse_eps, self.sparse_clip, device=table.device)
+                sparse_update = K.sparse_adagrad_rowwise if rowwise else K.sparse_adagrad
+                sparse_update(table, self.acc[name], E, rows, keys, grads, keys.numel(), self.sparse_lr,
+                              self.sparse_eps, self.sparse_clip, device=table.device)
         m._pending_sparse = []
 
 
@@ -710,7 +737,8 @@ class OneTransTrainer:
     def save_model(self, model_name: str, include_optimizer: bool = False) -> None:
         """train.py:281-297: weights, config.json, training_history.json.  ``include_optimizer`` adds
         ``optimizer_state.npz`` (OneTransOptimizer.state_dict: the dense slots, the step count and the tables'
-        Adagrad accumulators), so that a run resumed with ``load_model`` continues bit for bit; off by default,
+        Adagrad accumulators, per element or per row), so that a run resumed with ``load_model`` continues bit for
+        bit; off by default,
         the directory then holds the reference's three files.  Collective with a row-sharded table (every rank
         calls it; rank 0 writes the gathered arrays)."""
         path = self.model_dir / model_name
