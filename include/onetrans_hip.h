@@ -257,6 +257,12 @@ int ot_transpose_banks(const float* src, float* dst, const int64_t* banks_dev, i
 size_t ot_split_image_elems(int G, int N, int K);
 int ot_split_images(const float* base, const int64_t* desc_dev, int ndesc, int64_t total_units, uint16_t* img,
                     int precision, void* stream);
+/* How ot_split_images builds: 1 (default) = one launch, one workgroup per (bank, g, 128-column tile) that takes the
+ * tile's column maxima and then splits its K / 16 units; 0 = the two launches with one workgroup per unit (column
+ * scales, then the split), kept as the reference of tests/test_image_build_gpu.py.  Same image bytes either way.  The
+ * environment variable ONETRANS_IMAGE_BUILD (0 / 1) sets the process's initial value.  Process-wide; on = -1 only
+ * queries; returns the previous setting. */
+int ot_image_build(int on);
 /* ot_mixed_gemm / ot_mixed_gemm_rms with the B operand's pre-split image (b_image: the bank's image,
  * image_ntn column tiles per group, the GEMM's columns starting at tile image_tn0).  In split mode,
  * NT, whole tiles and 16-B aligned A rows the plane GEMM runs (B by global_load_lds from the image,

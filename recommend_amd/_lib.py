@@ -147,6 +147,7 @@ SIGNATURES = {
     'ot_ffn_fused_bwd_mask': (c_int, [P, c_uint32, P, I64, P]),
     'ot_bwd_mask_fused': (c_int, [c_int]),
     'ot_split_images': (c_int, [P, P, c_int, I64, P, c_int, P]),
+    'ot_image_build': (c_int, [c_int]),
     'ot_attn_fwd': (c_int, [P, I64, c_int, c_int, c_int, c_int, P, c_int, P, P, c_int, P]),
     'ot_attn_fwd_fp8_workspace_size': (c_size_t, [c_int, c_int, c_int, c_int]),
     'ot_attn_fwd_fp8': (c_int, [P, I64, c_int, c_int, c_int, c_int, P, c_int, P, P, P, c_size_t, P]),

@@ -468,6 +468,13 @@ def ffn_fused_bwd(dy2: Ptrish, lddy2: int, dy2_rowmax: Ptrish, dy2_rowmax_n: int
                    + 4.0 * M * (1 + dy2_rowmax_n), 3)
 
 
+def image_build(on: int = -1) -> int:
+    """ot_image_build: whether ``split_images`` is the one-launch build, one workgroup per (bank, g, column tile)
+    (1, default), or the two launches with one workgroup per unit (0: the tests' reference; same image bytes) — or
+    query (-1); returns the previous setting.  ``ONETRANS_IMAGE_BUILD`` sets the process's initial value."""
+    return _lib.size('ot_image_build', int(on))
+
+
 def split_images(base, desc_dev, ndesc, total_units, img) -> None:
     call('ot_split_images', ptr(base), ptr(desc_dev), ndesc, total_units, ptr(img), _prec(), stream())
 
