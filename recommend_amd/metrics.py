@@ -195,7 +195,7 @@ class StreamingMetrics:
     def __init__(self, tasks, device, num_thresholds: int = 200, binary_tasks=None, weighted: bool = False):
         import torch
         if binary_tasks is None:
-            from .model import BINARY_TASKS as binary_tasks
+            from .loss import BINARY_TASKS as binary_tasks
         self.tasks = list(tasks)
         self.binary = tuple(t in binary_tasks for t in self.tasks)
         self.device = torch.device(device)
@@ -318,7 +318,7 @@ class GroupedAUC:
     def __init__(self, tasks, device, capacity: int = 1 << 20, group_bits: int = 64, binary_tasks=None):
         import torch
         if binary_tasks is None:
-            from .model import BINARY_TASKS as binary_tasks
+            from .loss import BINARY_TASKS as binary_tasks
         self.tasks = list(tasks)
         self.binary = tuple(t in binary_tasks for t in self.tasks)
         self.device = torch.device(device)

@@ -8,8 +8,8 @@ training=...)`` (train.py:118, evaluate.py:87 — defect D4); ``reset_kv_cache()
 ``get_model_info()``; ``trainable_variables``; ``save_weights/load_weights``;
 ``create_onetrans_model(model_type)``.
 
-Autograd: four ``torch.autograd.Function``s (tokenizer, block, output-norm+heads, loss).  Their
-backward passes write parameter gradients straight into the flat gradient buffer
+Autograd: four ``torch.autograd.Function``s (tokenizer and output-norm+heads here, the block in block.py,
+the losses in loss.py).  Their backward passes write parameter gradients straight into the flat gradient buffer
 ``model.flat.grad`` (one bank per reference variable group), so the optimizer and the DP
 all-reduce each touch one contiguous buffer.  Embedding-table gradients are handed to the
 optimizer as (row keys, gradient rows) pairs: sparse updates, never a dense table gradient.
@@ -19,7 +19,7 @@ from __future__ import annotations
 
 import json
 import os
-from typing import Dict, List, Optional, Tuple
+from typing import Dict, List, Optional
 
 import numpy as np
 import torch
@@ -27,15 +27,14 @@ import torch.nn as nn
 
 from . import _lib
 from . import kernels as K
-from ._lib import (OT_AX_BF16, OT_AX_BF16_RMSNORM, OT_AX_GELU, OT_AX_RMSNORM, OT_EPI_ACCUMULATE, OT_EPI_AUX_BF16, OT_EPI_BIAS,
-                   OT_EPI_C_BF16, OT_EPI_DROPOUT, OT_EPI_GELU_BWD, OT_EPI_RESIDUAL, OT_EPI_RMSNORM_BWD,
-                   OT_EPI_ROW_RSTD, OT_EPI_ROWDOT, OT_GEMM_NN, OT_GEMM_NT, OT_WG_D_BF16, NS_FIELD_BYTES)
+from ._lib import OT_EPI_ACCUMULATE, OT_EPI_BIAS, OT_GEMM_NT, NS_FIELD_BYTES
+from .block import RMS_EPS, PairBounds, _Block, layer_seed
 from .config import (OneTransConfig, check_bag_features, check_ns_tokenizer, check_padding_mask, check_pyramid_select,
                      check_seq_fusion, check_weighted_loss, get_model_config)
-from .layout import TILE, FlatLayout, RowMap, build_map, head_map, identity_map, layer_maps, round_up
+from .layout import TILE, FlatLayout, build_map, head_map, identity_map, layer_maps, round_up
+from .loss import BINARY_TASKS, keras_bce_loss  # noqa: F401  (re-exported: callers import them from here)
 from .params import init_params, ns_table_offsets
 
-RMS_EPS = 1e-6   # RMSNorm eps, model.py:14
 NS_GROUPS_KEY = '__ns_token_groups__'   # save_weights: the groups of a group-wise NS tokenizer (JSON), next to the banks
 
 
@@ -178,620 +177,6 @@ def _seq_out_rows(plan, sm):
     return rows if rows is not None else sm['rows'][0]
 
 
-def layer_seed(seed: int, b0: int, I: int, d: int) -> int:
-    """Dropout seed of a layer whose local sample b is global sample b0 + b.  The mask hashes the 32-bit
-    element index (b*I + p)*d + n as idx * 0x9E3779B1 + seed (common.h drop_keep), so shifting every
-    index by b0*I*d is the same as adding b0*I*d*0x9E3779B1 to the seed (mod 2^32): the kernels keep
-    local indices and the masks equal the full batch's (oracle dropout_scale's ``b0``)."""
-    return (seed + b0 * I * d * 0x9E3779B1) & 0xFFFFFFFF if b0 else seed
-
-
-def _layer_valid(kvalid, I):
-    """The slice of layer 0's key-padding mask [B, L0] that a layer of I tokens reads under the tail keep: its last I
-    columns, as (tensor, element offset, row stride) — the same array, no copy."""
-    L0 = kvalid.shape[1]
-    return kvalid, L0 - I, L0
-
-
-def _attn_qpos(cfg, pos):
-    """Kept-query positions for the attention kernels: None (the tail rule, I - K + j) when the keep is
-    the reference's tail — ot_pyramid_select returns exactly that set there, in order."""
-    return None if getattr(cfg, 'pyramid_select', 'tail') == 'tail' else pos
-
-
-class PairBounds:
-    """Magnitude bounds of the fp16-pair weight gradients' operands (split mode, ot_mixed_gemm_wgrad_ex) for one
-    forward and its backward: a zeroed float per layer and slot, into which the producing kernel folds max |output|
-    (an atomic max: the recompute's second fold of the same values changes nothing).  ``out`` is the producer's
-    view; ``get`` the consumer's, None unless a producer took it — no bound, like no object: the exact split."""
-    SLOTS = ('o', 'u', 'dy2', 'du', 'dyo', 'dqkv', 'dx')   # |O|, |U|, |dY2|, |dU|, |dX1 masked|, |dQKV|, |dX|
-
-    def __init__(self, layers: int, device):
-        self.t, self._taken = torch.zeros(layers, 8, device=device), {}
-        self._dx = {}
-
-    def put_dx(self, l: int, dx: torch.Tensor, rowabs: torch.Tensor) -> None:
-        """Block ``l``'s input gradient with the row maxima (and, in slot 'dx', the bound) its QKV dgrad reported:
-        block ``l - 1`` masks this tensor inside its fused FFN backward (``bwd_mask_gate``)."""
-        self._dx[l] = (dx, dx._version, rowabs)
-
-    def take_dx(self, l: int, dx2: torch.Tensor):
-        """(row maxima, bound) of ``dx2`` if it is the tensor block ``l`` reported, unchanged since; else None."""
-        e = self._dx.pop(l, None)
-        if (e is None or e[0].data_ptr() != dx2.data_ptr() or e[0].shape != dx2.shape or e[1] != dx2._version
-                or not dx2.is_contiguous()):
-            return None
-        return e[2], self.get(l, 'dx')
-
-    @classmethod
-    def begin(cls, layers: int, device, mode: str, pair_wgrad: bool) -> Optional['PairBounds']:
-        """For a forward in split mode with ONETRANS_PAIR_WGRAD on that a backward can follow; else None."""
-        return cls(layers, device) if mode == 'split' and pair_wgrad and torch.is_grad_enabled() else None
-
-    def out(self, l: int, name: str) -> torch.Tensor:
-        return self._taken.setdefault((l, name), self.t[l, self.SLOTS.index(name):][:1])
-
-    def get(self, l: int, name: str) -> Optional[torch.Tensor]:
-        return self._taken.get((l, name))
-
-
-def a_row_bounds(on: bool, x, ld: int, rows: int, n: int, reported=None) -> Dict:
-    """The GEMM arguments that hand an fp16-pair image (``on``: gemm_pair) its A rows' maxima: those x's producer
-    ``reported``, else one row-absmax pass over x [rows, n]."""
-    if on and reported is None:
-        reported = torch.empty(rows, (n + 255) // 256, device=x.device)
-        K.rows_absmax(x, ld, rows, n, reported)
-    return dict(a_rowmax=reported, a_rowmax_n=reported.shape[1]) if on else {}
-
-
-def bwd_mask_gate(m, l: int, rate: float, bounds, kvalid) -> bool:
-    """Does block ``l``'s backward mask dx2 inside the fused FFN backward and the W2 weight gradient (no dropout
-    pass, no dY2)?  Where ot_ffn_fused_bwd's form applies under dropout, with the pair weight gradients'
-    bounds, no padding mask, and ONETRANS_BWD_MASK_FUSED / K.bwd_mask_fused on."""
-    cfg = m.config
-    d, f = cfg.hidden_dim, cfg.ffn_dim
-    return bool(l >= 0 and rate > 0 and bounds is not None and kvalid is None and K.matmul_mode() == 'split'
-                and m.fuse_bwd and d == TILE and f % TILE == 0 and f <= K.FFN_FUSED_MAX_F
-                and m.dgrad_pair(f'blk.{l}.w2') and m.dgrad_pair(f'blk.{l}.w1')
-                and K.ffn_fused_bwd_on() and K.bwd_mask_fused())
-
-
-def _block_forward(m, l, x, I, Kq, seed, training, rstd_in=None, select=False, need_out=True, need_u=True,
-                   bounds=None, kvalid=None):
-    """The block's forward kernels (``_Block.forward``; also the backward's recompute with
-    ``need_out=False``, which stops after FFN1: the backward needs u, not the block output).
-    ``need_u=False`` (no backward will read this call's u): the fused FFN forward does not write it (saved u None).
-    ``bounds``: this forward's PairBounds or None.
-    ``kvalid``: layer 0's key-padding mask [B, L0] (uint8; seq_padding_mask) or None; the layer reads its last I columns.
-    Returns (x2, rstd_out, saved, pos, inv, rate); saved = (x, rstd1, qkv, o, lse, x1, rstd2, u, h, xn1, x1n, yf);
-    h = the stored bf16 gelu(u), xn1 / x1n = the bf16 normalised QKV / FFN1 inputs (bf16 mode) or None, yf = the folded
-    attention's probability-weighted raw rows [B, H, d] (``fold_gate``) or None."""
-    cfg = m.config
-    d, f, H = cfg.hidden_dim, cfg.ffn_dim, cfg.num_heads
-    hd = d // H
-    B = x.shape[0] // I
-    dev = x.device
-    maps = m.maps(B, I, Kq)
-    ma, mt = maps['all'].to(dev), maps['tail'].to(dev)
-    na, nt = maps['all'].ntiles, maps['tail'].ntiles
-    rate = cfg.dropout_rate if training else 0.0
-    dflag = OT_EPI_DROPOUT if rate > 0 else 0
-    wqkv, wo = m.pT(f'blk.{l}.wqkv'), m.pT(f'blk.{l}.wo')          # transposed shadow: [G][N][K]
-    w1, b1, w2, b2 = m.pT(f'blk.{l}.w1'), m.p(f'blk.{l}.b1'), m.pT(f'blk.{l}.w2'), m.p(f'blk.{l}.b2')
-    g1, g2 = m.p(f'blk.{l}.norm1'), m.p(f'blk.{l}.norm2')
-    fuse = m.fuse_with((f'blk.{l}.wo', 'fwd'), (f'blk.{l}.w2', 'fwd'))
-    # norm1 -> rstd only; the QKV GEMM applies it in its A prologue
-    if rstd_in is not None and rstd_in.numel() == B * I:
-        rstd1 = rstd_in
-    else:
-        rstd1 = torch.empty(B * I, device=dev)
-        K.rmsnorm_fwd(x, d, B * I, d, rstd1, eps=RMS_EPS)
-    # pyramid keep (model.py:287-302, 371): the kept query positions come from the wavefront
-    # top-K select (ot_pyramid_select); with no score (reference semantics) they are the tail
-    qrows, pos, inv = mt['rows'][0], None, None
-    if select:
-        pos = torch.empty(B * Kq, dtype=torch.int32, device=dev)
-        inv = torch.empty(B * I, dtype=torch.int32, device=dev)
-        if cfg.pyramid_select == 'norm':
-            # score = token RMS (1/rstd1): keep the largest; the NS tail is always kept and only the
-            # shared-group rows of the tail map change (dedicated_positions='tail', checked in config)
-            nf = min(cfg.num_ns_tokens, Kq)
-            qrows = qrows.clone()
-            K.pyramid_select(B, I, Kq, pos, inv, score=rstd1, sign=-1.0, nforce=nf, map_rows=qrows,
-                             map_per_sample=Kq - nf)
-        else:
-            K.pyramid_select(B, I, Kq, pos, inv)
-    tail = (Kq, I, pos)
-    # bf16 mode: the block input in bf16 as the previous block's FFN2 epilogue stored it (ot_rms_epilogue
-    # .c16_out) — the QKV GEMM reads it (OT_AX_BF16_RMSNORM: the values its fragments would round x to)
-    x16 = m.take_x16(l, x) if d % TILE == 0 and need_out else None
-    ax1 = OT_AX_BF16_RMSNORM if x16 is not None else OT_AX_RMSNORM
-    xa = x16 if x16 is not None else x
-    qkv = torch.empty(B * I, 3 * d, device=dev)
-    # bf16 mode, training: the QKV / FFN1 GEMMs also store their normalised A rows in bf16 (ot_rms_epilogue
-    # .xn_out) for the copy-staged bf16 weight gradients of Wqkv / W1 (operands read once, no norm re-applied)
-    xn_on = (training and K.matmul_mode() == 'bf16' and d % TILE == 0
-             and m.bimg(f'blk.{l}.wqkv') is not None)
-    xn1 = torch.empty(B * I, d, dtype=torch.int16, device=dev) if xn_on else None
-    x1n = torch.empty(B * Kq, d, dtype=torch.int16, device=dev) if xn_on else None
-    # the last layer's one query, folded through the shared K / V projection (ot_attn_fold_*, DESIGN.md §5)
-    fold = m.fold_gate(I, Kq, select, kvalid)
-    yf = None
-    if xn1 is not None:
-        full = Kq == I
-        K.gemm_rms(OT_GEMM_NT, xa, d, d, ma['rows'][0], wqkv if full else (wqkv, d * d), 3 * d * d, d,
-                   3 * d if full else 2 * d, ma['tile_group'], na, qkv if full else (qkv, d), 3 * d, ma['rows'][0],
-                   epi=0, a_xform=ax1, rstd=rstd1, gamma=g1, m_rows=maps['all'].nrows, device=dev,
-                   bimg=m.bimg(f'blk.{l}.wqkv') if full else m.bimg(f'blk.{l}.wqkv', tn0=d // TILE),
-                   xn_out=xn1, ldxn=d)
-        if not full:
-            K.gemm(OT_GEMM_NT, xa, d, d, qrows, wqkv, 3 * d * d, d, d, mt['tile_group'], nt, qkv,
-                   3 * d, qrows, a_xform=ax1, rstd=rstd1, gamma=g1, m_rows=maps['tail'].nrows,
-                   bimg=m.bimg(f'blk.{l}.wqkv'))
-    elif Kq == I:
-        K.gemm(OT_GEMM_NT, xa, d, d, ma['rows'][0], wqkv, 3 * d * d, d, 3 * d, ma['tile_group'], na, qkv,
-               3 * d, ma['rows'][0], a_xform=ax1, rstd=rstd1, gamma=g1, m_rows=maps['all'].nrows,
-               bimg=m.bimg(f'blk.{l}.wqkv'))
-    else:
-        # one query and shared-weight keys (fold): K / V of the dedicated rows only (and the query row, which the
-        # map holds for the backward) — the attention reads the other keys' raw rows
-        mkv, kvm = (maps['fold'].to(dev), maps['fold']) if fold is not None else (ma, maps['all'])
-        K.gemm(OT_GEMM_NT, xa, d, d, mkv['rows'][0], (wqkv, d * d), 3 * d * d, d, 2 * d, mkv['tile_group'],
-               kvm.ntiles, (qkv, d), 3 * d, mkv['rows'][0], a_xform=ax1, rstd=rstd1, gamma=g1, m_rows=kvm.nrows,
-               bimg=m.bimg(f'blk.{l}.wqkv', tn0=d // TILE) if d % TILE == 0 else None)
-        K.gemm(OT_GEMM_NT, xa, d, d, qrows, wqkv, 3 * d * d, d, d, mt['tile_group'], nt, qkv,
-               3 * d, qrows, a_xform=ax1, rstd=rstd1, gamma=g1, m_rows=maps['tail'].nrows,
-               bimg=m.bimg(f'blk.{l}.wqkv'))
-    o = torch.empty(B * Kq, d, device=dev)
-    lse = torch.empty(B * H * Kq, device=dev)
-    # a 'tail' keep (reference rule) is the contiguous tail, which the attention kernels address
-    # arithmetically (no per-query position loads; C3 attention 20.2 -> 18.3 ms/step); the select map
-    # still drives the GEMM row maps and epilogues
-    # fp8 training forward: qkv's operands are replaced by their dequantised fp8 values, so the backward
-    # differentiates (nearly) the forward that ran (OT_FP8_DEQUANT; exact for one-term operands, approximate
-    # for the default two-term ones: bf16 rounding of hi + lo and the dropped lo.lo product)
-    # with the key-grouped bf16 backward, the dequantised operands go to a bf16 copy that replaces qkv as the
-    # backward's saved operand (the backward rounds them to bf16 anyway)
-    qp_f = _attn_qpos(cfg, pos)
-    qkv16 = (torch.empty(B * I, 3 * d, dtype=torch.int16, device=dev)
-             if m.attn_fp8 and training and K.attn_bwd_bf16_supported(I, Kq, hd, qp_f) else None)
-    out = (lambda name: bounds.out(l, name)) if bounds is not None else (lambda name: None)
-    # the Wo forward on the fp16 pair (pair-form Wo image): O's row maxima, per head, and |O| from the slice forward
-    pwo_f = m.gemm_pair(f'blk.{l}.wo', 'fwd')
-    # (the masked attention reports no bounds: O's row maxima then come from a_row_bounds' own pass, and the Wo weight
-    # gradient, without |O|, runs the exact split)
-    # (nor does the folded attention: its B rows go through the row-absmax pass and the exact-split Wo gradient)
-    o_rep = kvalid is None and not m.attn_fp8 and fold is None and K.attn_amax_supported(I, Kq, hd, qp_f)
-    rm_o = torch.empty(B * Kq, H, device=dev) if pwo_f and o_rep else None
-    if fold is not None:
-        yf = torch.empty(B * H, d, device=dev)
-        K.attn_fold_fwd(x, d, rstd1, g1, m.p(f'blk.{l}.wqkv'), 3 * d, wqkv, d, qkv, 3 * d, B, H, I, hd, fold, o, lse,
-                        yf)
-    elif kvalid is not None:
-        K.attn_fwd_masked(qkv, 3 * d, B, H, I, Kq, hd, o, lse, _layer_valid(kvalid, I), qpos=qp_f)
-    else:
-        K.attn_fwd(qkv, 3 * d, B, H, I, Kq, hd, o, lse, qpos=qp_f, fp8=m.attn_fp8, dequant=m.attn_fp8 and training,
-                   fp8_terms=m.fp8_terms, deq16=qkv16, amax=out('o') if o_rep else None, rowmax=rm_o)
-    pa_o = a_row_bounds(pwo_f, o, d, B * Kq, d, rm_o)
-    if qkv16 is not None:
-        qkv = qkv16
-    # x1 = x[tail] + drop(o @ Wo)      (model.py:117, 193)
-    x1 = torch.empty(B * Kq, d, device=dev)
-    rstd2 = torch.empty(B * Kq, device=dev)
-    x1_16 = None
-    if fuse:
-        # the bf16 residual copy feeds FFN1 only as an OT_AX_BF16_RMSNORM operand, which needs W1's plane image
-        x1_16 = (torch.empty(B * Kq, d, dtype=torch.int16, device=dev)
-                 if m.x16_on(d) and m.bimg(f'blk.{l}.w1') is not None else None)
-        K.gemm_rms(OT_GEMM_NT, o, d, d, mt['rows'][1], wo, 0, d, d, mt['tile_group'], nt, x1, d, mt['rows'][1],
-                   epi=OT_EPI_RESIDUAL | dflag | OT_EPI_ROW_RSTD, res=x, ldres=d, res_tok=1, seed=seed,
-                   site=2 * l, drop=rate, tail=tail, m_rows=maps['tail'].nrows, rstd_out=rstd2, eps=RMS_EPS,
-                   bimg=m.bimg(f'blk.{l}.wo'), c16_out=x1_16, ldc16=d, device=dev, **pa_o)
-    else:
-        K.gemm_rms(OT_GEMM_NT, o, d, d, mt['rows'][1], wo, 0, d, d, mt['tile_group'], nt, x1, d, mt['rows'][1],
-                   epi=OT_EPI_RESIDUAL | dflag, res=x, ldres=d, res_tok=1, seed=seed, site=2 * l, drop=rate,
-                   tail=tail, m_rows=maps['tail'].nrows, bimg=m.bimg(f'blk.{l}.wo'), device=dev, **pa_o)
-        K.rmsnorm_fwd(x1, d, B * Kq, d, rstd2, eps=RMS_EPS)
-    # u = norm2(x1) @ W1[g] + b1[g]  (pre-activation; GELU applied by its consumers)
-    # bf16 mode: the FFN1 epilogue also stores h = gelu(u) rounded to bf16 — exactly the operand the bf16
-    # FFN2 GEMM would form at fragment time — so FFN2 reads 2 B per element and evaluates no erf (it did,
-    # once per output column tile), and the W2 weight gradient reuses h
-    w2img = m.bimg(f'blk.{l}.w2')
-    h = (torch.empty(B * Kq, f, dtype=torch.int16, device=dev)
-         if K.matmul_mode() == 'bf16' and w2img is not None
-         and m.bimg(f'blk.{l}.w1') is not None and f % TILE == 0 else None)
-    # ... and u itself in bf16 (as a bf16 Keras policy stores it): its one reader is then the FFN2 dgrad's
-    # GELU' / row-dot epilogue (OT_EPI_AUX_BF16), which needs the fused norm2 backward's bf16-dU form
-    u_bf = h is not None and m.fuse_bwd2 and not m.fuse_bwd and f % TILE == 0
-    u = torch.empty(B * Kq, f, device=dev, dtype=torch.int16 if u_bf else torch.float32)
-    # split mode: the FFN1 epilogue also writes each column tile's row maximum of u, from which the FFN2 plane GEMM
-    # takes its rows' fp16-pair scales (its W2 image is in the pair form, layout kscale -2)
-    # (exactly when W2's forward image is in the pair form, layout.pair_images: then W1's forward image exists, f % 128
-    # == 0, and the FFN1 plane GEMM below writes every row's maxima; the library refuses rowmax_out anywhere else and a
-    # pair image read without them multiplies NaN into the output)
-    pair_w2 = K.matmul_mode() == 'split' and w2img is not None and (f'blk.{l}.w2', 'fwd') in m.layout.pair_images
-    assert not pair_w2 or (h is None and m.bimg(f'blk.{l}.w1') is not None and f % TILE == 0), \
-        'the pair-form W2 image needs the FFN1 plane GEMM to write the row maxima of u'
-    # split mode, d == 128, the block output wanted: FFN1 -> GELU -> FFN2 in one launch (ot_ffn_fused_fwd: u stays in
-    # the accumulators, no row maxima round trip); the recompute (need_out False) wants u only: the FFN1 launch
-    if (pair_w2 and need_out and d == TILE and f <= K.FFN_FUSED_MAX_F and x1_16 is None and K.ffn_fused()):
-        if not need_u:
-            u = None
-        x2 = torch.empty(B * Kq, d, device=dev)
-        rstd_out = torch.empty(B * Kq, device=dev) if fuse else None
-        K.ffn_fused_fwd(x1, d, mt['rows'][1], mt['tile_group'], nt, rstd2, m.bimg(f'blk.{l}.w1')[0],
-                        m.layout.images[(f'blk.{l}.w1', 'fwd')][1], w2img[0],
-                        m.layout.images[(f'blk.{l}.w2', 'fwd')][1], b1, f, b2, d, f, x2, d, u_out=u, ldu=f,
-                        u_amax=out('u'), rstd_out=rstd_out, eps=RMS_EPS, seed=seed, site=2 * l + 1, drop=rate,
-                        tail=tail, m_rows=maps['tail'].nrows)
-        saved = (x, rstd1, qkv, o, lse, x1, rstd2, u, None, xn1, None, yf)
-        return x2, rstd_out, saved, pos, inv, rate
-    umax = torch.empty(B * Kq, f // TILE, device=dev) if pair_w2 else None
-    if h is not None:
-        K.gemm_rms(OT_GEMM_NT, x1 if x1_16 is None else x1_16, d, d, mt['rows'][1], w1, d * f, d, f,
-                   mt['tile_group'], nt, u, f, mt['rows'][1],
-                   a_xform=OT_AX_RMSNORM if x1_16 is None else OT_AX_BF16_RMSNORM, rstd=rstd2, gamma=g2, bias=b1,
-                   bias_gstride=f,
-                   epi=OT_EPI_BIAS | (OT_EPI_C_BF16 if u_bf else 0),
-                   m_rows=maps['tail'].nrows, bimg=m.bimg(f'blk.{l}.w1'), gelu_out=h, ldgelu=f,
-                   xn_out=x1n, ldxn=d)
-    elif umax is not None:
-        K.gemm_rms(OT_GEMM_NT, x1 if x1_16 is None else x1_16, d, d, mt['rows'][1], w1, d * f, d, f, mt['tile_group'],
-                   nt, u, f, mt['rows'][1], a_xform=OT_AX_RMSNORM if x1_16 is None else OT_AX_BF16_RMSNORM,
-                   rstd=rstd2, gamma=g2, bias=b1, bias_gstride=f, epi=OT_EPI_BIAS, m_rows=maps['tail'].nrows,
-                   bimg=m.bimg(f'blk.{l}.w1'), rowmax_out=umax, rowmax_n=umax.shape[1],
-                   amax_out=out('u'))                 # |U| >= |gelu(U)|: the W2 wgrad's A bound
-    else:
-        K.gemm(OT_GEMM_NT, x1 if x1_16 is None else x1_16, d, d, mt['rows'][1], w1, d * f, d, f, mt['tile_group'],
-               nt, u, f, mt['rows'][1], a_xform=OT_AX_RMSNORM if x1_16 is None else OT_AX_BF16_RMSNORM, rstd=rstd2,
-               gamma=g2, bias=b1, bias_gstride=f, epi=OT_EPI_BIAS, m_rows=maps['tail'].nrows,
-               bimg=m.bimg(f'blk.{l}.w1'))
-    if x1n is not None and h is None:                # the FFN1 GEMM above did not store it
-        x1n = None
-    saved = (x, rstd1, qkv, o, lse, x1, rstd2, u, h, xn1, x1n, yf)
-    if not need_out:
-        return None, None, saved, pos, inv, rate
-    # x2 = x1 + drop(gelu(u) @ W2[g] + b2[g])     (model.py:154-161, 198)
-    x2 = torch.empty(B * Kq, d, device=dev)
-    rstd_out = None
-    a2, ax2 = (h, OT_AX_BF16) if h is not None else (u, OT_AX_GELU)
-    pa_u = a_row_bounds(pair_w2, u, f, B * Kq, f, umax)
-    if fuse:
-        rstd_out = torch.empty(B * Kq, device=dev)
-        x2_16 = torch.empty(B * Kq, d, dtype=torch.int16, device=dev) if m.x16_on(d) and w2img is not None else None
-        K.gemm_rms(OT_GEMM_NT, a2, f, f, mt['rows'][1], w2, f * d, f, d, mt['tile_group'], nt, x2, d,
-                   mt['rows'][1], a_xform=ax2, bias=b2, bias_gstride=d,
-                   epi=OT_EPI_BIAS | OT_EPI_RESIDUAL | dflag | OT_EPI_ROW_RSTD, res=x1, ldres=d, res_tok=0,
-                   seed=seed, site=2 * l + 1, drop=rate, tail=tail, m_rows=maps['tail'].nrows,
-                   rstd_out=rstd_out, eps=RMS_EPS, bimg=w2img, c16_out=x2_16, ldc16=d, **pa_u)
-        m.put_x16(l + 1, x2, x2_16)
-    elif umax is not None:
-        K.gemm_rms(OT_GEMM_NT, a2, f, f, mt['rows'][1], w2, f * d, f, d, mt['tile_group'], nt, x2, d, mt['rows'][1],
-                   a_xform=ax2, bias=b2, bias_gstride=d, epi=OT_EPI_BIAS | OT_EPI_RESIDUAL | dflag, res=x1,
-                   ldres=d, res_tok=0, seed=seed, site=2 * l + 1, drop=rate, tail=tail,
-                   m_rows=maps['tail'].nrows, bimg=w2img, **pa_u)
-    else:
-        K.gemm(OT_GEMM_NT, a2, f, f, mt['rows'][1], w2, f * d, f, d, mt['tile_group'], nt, x2, d, mt['rows'][1],
-               a_xform=ax2, bias=b2, bias_gstride=d, epi=OT_EPI_BIAS | OT_EPI_RESIDUAL | dflag, res=x1,
-               ldres=d, res_tok=0, seed=seed, site=2 * l + 1, drop=rate, tail=tail,
-               m_rows=maps['tail'].nrows, bimg=w2img)
-    return x2, rstd_out, saved, pos, inv, rate
-
-
-class _Block(torch.autograd.Function):
-    """OneTransBlock.call (model.py:186-200) for the last K of I tokens (pyramid / last-layer DCE).
-    x: [B*I, d] -> ([B*K, d], rstd of the output rows).
-
-    When d == 128 (one GEMM tile holds whole rows) the RMSNorms are fused into the GEMMs around
-    them: the Wo / FFN2 epilogues emit the rstd of the rows they finish (norm2 of this block, norm1
-    of the next: ``rstd_in``), and the FFN1 / QKV dgrad epilogues apply the norm backward."""
-
-    @staticmethod
-    def forward(ctx, flat, x, m, l, I, Kq, seed, training, rstd_in=None, select=False, bounds=None, kvalid=None):
-        # u is read by a backward only: with the recompute (which forms it again) or no input that needs a gradient
-        # (inference) this forward need not write it
-        x2, rstd_out, saved, pos, inv, rate = _block_forward(
-            m, l, x, I, Kq, seed, training, rstd_in, select, bounds=bounds,
-            need_u=not m.recompute and any(ctx.needs_input_grad), kvalid=kvalid)
-        if m.recompute:
-            # activation recompute: keep the block input (and its rstd); the backward re-runs the
-            # forward kernels up to FFN1 (dropout masks and pyramid keeps are deterministic)
-            ctx.save_for_backward(saved[0], saved[1])
-            ctx.fwd_args = (training, select)
-        else:
-            ctx.save_for_backward(*saved)
-        ctx.m, ctx.l, ctx.I, ctx.Kq, ctx.seed, ctx.rate = m, l, I, Kq, seed, rate
-        ctx.pos, ctx.inv, ctx.bounds, ctx.kvalid = pos, inv, bounds, kvalid
-        if rstd_out is None:
-            rstd_out = x2.new_empty(0)          # not fused: the next block computes its own rstd
-        ctx.mark_non_differentiable(rstd_out)
-        return x2, rstd_out
-
-    @staticmethod
-    def backward(ctx, dx2, _drstd=None):
-        # the autograd engine runs this on its own thread: enter the model's precision there
-        with K.precision(ctx.m.matmul):
-            return _Block._backward(ctx, dx2, _drstd)
-
-    @staticmethod
-    def _backward(ctx, dx2, _drstd=None):
-        m, l, I, Kq, seed, rate = ctx.m, ctx.l, ctx.I, ctx.Kq, ctx.seed, ctx.rate
-        pos, inv, bounds, kvalid = ctx.pos, ctx.inv, ctx.bounds, ctx.kvalid
-        if m.recompute:
-            xin, rstd_in = ctx.saved_tensors
-            training, select = ctx.fwd_args
-            _, _, saved, pos, inv, _ = _block_forward(m, l, xin, I, Kq, seed, training, rstd_in, select,
-                                                      need_out=False, bounds=bounds, kvalid=kvalid)
-            x, rstd1, qkv, o, lse, x1, rstd2, u, h, xn1, x1n, yf = saved
-        else:
-            x, rstd1, qkv, o, lse, x1, rstd2, u, h, xn1, x1n, yf = ctx.saved_tensors
-        tail = (Kq, I, pos)
-        cfg = m.config
-        d, f, H = cfg.hidden_dim, cfg.ffn_dim, cfg.num_heads
-        hd = d // H
-        B = x.shape[0] // I
-        dev = x.device
-        acc = m.accumulate_grads
-        maps = m.maps(B, I, Kq)
-        ma, mt = maps['all'].to(dev), maps['tail'].to(dev)
-        na, nt = maps['all'].ntiles, maps['tail'].ntiles
-        nca, nct = maps['all'].chunks.shape[0], maps['tail'].chunks.shape[0]
-        G = cfg.num_groups
-        dx2 = dx2.contiguous()
-        rowdot = None
-        fused2 = m.fuse_bwd2 and not m.fuse_bwd and f % TILE == 0
-        du_bf = (fused2 and h is not None and m.bimg(f'blk.{l}.w1', 'dgrad') is not None)
-        # FFN branch: dY2 = mask(dx2) — in bf16 with the bf16 dU path (its two readers, the FFN2 dgrad's A and
-        # the W2 weight gradient's D, round it to bf16; the latter then runs copy-staged)
-        # fp16-pair weight gradients (split mode): their operands' bounds (PairBounds; None = the exact split runs):
-        # |U| and |O| where this backward's own forward took them; ``keep`` goes with the side stream's reads (m.side)
-        out = (lambda name: bounds.out(l, name)) if bounds is not None else (lambda name: None)
-        b_o, b_u = (bounds.get(l, 'o'), bounds.get(l, 'u')) if bounds is not None else (None, None)
-        keep = (bounds.t,) if bounds is not None else ()
-        # fp16-pair dgrads (pair-form dgrad images): the A rows' maxima, from the producers where they report them
-        pw2, pw1, pwo = (m.dgrad_pair(f'blk.{l}.{w}') for w in ('w2', 'w1', 'wo'))
-        # split mode, d == 128, pair-form W2 / W1 dgrad images, float32 dU, the norm2 backward in the FFN1 dgrad's
-        # epilogue: both input gradients in one launch (ot_ffn_fused_bwd: dU is written for the W1 weight gradient but not
-        # read back, and its row maxima stay in registers)
-        ffn_bwd = (pw2 and pw1 and m.fuse_bwd and d == TILE and f % TILE == 0 and f <= K.FFN_FUSED_MAX_F
-                   and not du_bf and h is None and bool(K.ffn_fused_bwd_on()))
-        # ... and under dropout with the mask inside it (ot_ffn_fused_bwd_mask) and inside the W2 weight gradient
-        # (OT_WG_D_KEEPBITS, from the keep bits that kernel writes): no dropout pass, dY2 never exists.  dx2's row
-        # maxima and bound come from its producer, the QKV dgrad of the block above, else from one row-absmax pass
-        mask_fused = ffn_bwd and b_u is not None and bwd_mask_gate(m, l, rate, bounds, kvalid)
-        dx_rep = bounds.take_dx(l + 1, dx2) if bounds is not None else None
-        dy2_rep = rate > 0 and not du_bf           # the float32 dropout reports |dY2|, and row maxima at some widths
-        b_dy2 = out('dy2') if dy2_rep and not mask_fused else None
-        rm_dy2 = (torch.empty(B * Kq, (d + 255) // 256, device=dev)
-                  if dy2_rep and pw2 and K.dropout_rowmax_supported(d) and not mask_fused else None)
-        dy2 = dx2
-        if mask_fused:
-            if dx_rep is not None:
-                rm_dy2, b_dy2 = dx_rep             # (of dx2: both kernels multiply by 1 / (1 - rate))
-            else:
-                rm_dy2 = torch.empty(B * Kq, 1, device=dev)
-                K.rows_absmax(dx2, d, B * Kq, d, rm_dy2)
-                b_dy2 = rm_dy2.max().reshape(1)
-            keep_bits = torch.empty(B * Kq, d // 32, dtype=torch.int32, device=dev)
-        elif rate > 0:
-            dy2 = torch.empty(B * Kq, d, device=dev, dtype=torch.int16 if du_bf else torch.float32)
-            K.dropout_apply(dx2, d, dy2, d, B * Kq, d, seed, 2 * l + 1, rate, tail, amax=b_dy2, rowmax=rm_dy2)
-        pa2 = a_row_bounds(pw2, dy2, d, B * Kq, d, rm_dy2)
-        dy_bf = dy2.dtype == torch.int16
-        # bf16 mode (C5): dU is stored in bf16 by the FFN2 dgrad epilogue (OT_EPI_C_BF16); its two consumers,
-        # the FFN1 dgrad (bf16 A, plane GEMM) and the W1 weight gradient (OT_WG_D_BF16), rounded it to bf16 at
-        # fragment / staging time anyway, so only b1's gradient (a column sum of dU) sees the rounding
-        du = torch.empty(B * Kq, f, device=dev, dtype=torch.int16 if du_bf else torch.float32)
-        cbf = OT_EPI_C_BF16 if du_bf else 0
-        # bf16 mode with the fused norm2 backward (C5): the FFN2 dgrad epilogue, which reads U for GELU'
-        # anyway, also stores gelu(U) in bf16 — the W2 weight gradient then reads 2 B per element instead of
-        # U's 4 and evaluates no erf (it did, once per output column tile: 4x at f = 2048, d = 512)
-        # (the forward's FFN1 epilogue stored it already when h is not None)
-        hbf = (torch.empty(B * Kq, f, dtype=torch.int16, device=dev)
-               if h is None and fused2 and K.matmul_mode() == 'bf16' else None)
-        if hbf is None and not mask_fused:
-            with m.side(u if h is None else h, dy2, *keep):   # weight gradients overlap the dgrad chain (second stream)
-                K.wgrad(u if h is None else h, f, mt['rows'][1], dy2, d, mt['rows'][1], f, d, mt, nct, G,
-                        m.g(f'blk.{l}.w2'), f * d, m.g(f'blk.{l}.b2'), d,
-                        a_xform=(OT_AX_GELU if h is None else OT_AX_BF16) | (OT_WG_D_BF16 if dy_bf else 0),
-                        accumulate=acc, device=dev, m_rows=maps['tail'].nrows, rowmap=maps['tail'],
-                        a_bound=b_u if h is None else None, d_bound=b_dy2)
-        # does the FFN2 dgrad report dU's bound and row maxima?  (its whole-tile vector epilogue does)
-        du_rep = fused2 or (((bounds is not None and not du_bf) or pw2 or pw1) and f % TILE == 0)
-        b_du = out('du') if du_rep and not du_bf else None
-        rm_du = torch.empty(B * Kq, f // TILE, device=dev) if pw1 and du_rep and not ffn_bwd else None
-        rep_du = dict(amax_out=b_du, rowabs_out=rm_du, rowabs_n=f // TILE if rm_du is not None else 0)
-        if ffn_bwd:
-            dx1 = torch.empty(B * Kq, d, device=dev)
-            dyo = torch.empty(B * Kq, d, device=dev) if rate > 0 else dx1
-            rm_dyo = torch.empty(B * Kq, 1, device=dev) if pwo else None
-            b_dyo = out('dyo')
-            K.ffn_fused_bwd(dy2, d, pa2['a_rowmax'], pa2['a_rowmax_n'], mt['rows'][1], mt['tile_group'], nt,
-                            m.bimg(f'blk.{l}.w2', 'dgrad')[0], m.layout.images[(f'blk.{l}.w2', 'dgrad')][1],
-                            m.bimg(f'blk.{l}.w1', 'dgrad')[0], m.layout.images[(f'blk.{l}.w1', 'dgrad')][1], f,
-                            u, f, du, f, x1, d, m.p(f'blk.{l}.norm2'), rstd2, dx1, d, m.g(f'blk.{l}.norm2'),
-                            du_amax=b_du, dres=dx2, lddres=d, dx_masked=dyo if rate > 0 else None, lddxm=d,
-                            accumulate_dgamma=acc, amax_out=b_dyo, rowabs_out=rm_dyo,
-                            rowabs_n=1 if rm_dyo is not None else 0, seed=seed, site=2 * l, drop=rate, tail=tail,
-                            m_rows=maps['tail'].nrows, device=dev, mask_site=2 * l + 1 if mask_fused else None,
-                            keep_out=keep_bits if mask_fused else None, ldkeep=d // 32)
-            if mask_fused:
-                with m.side(u, dx2, keep_bits, b_dy2, *keep):   # after the launch that writes the keep bits
-                    K.wgrad(u, f, mt['rows'][1], dx2, d, mt['rows'][1], f, d, mt, nct, G, m.g(f'blk.{l}.w2'), f * d,
-                            m.g(f'blk.{l}.b2'), d, a_xform=OT_AX_GELU | _lib.OT_WG_D_KEEPBITS, accumulate=acc,
-                            device=dev, m_rows=maps['tail'].nrows, rowmap=maps['tail'], a_bound=b_u, d_bound=b_dy2,
-                            keep=keep_bits, ldkeep=d // 32, d_scale=1.0 / (1.0 - rate))
-        elif fused2:
-            # d > 128: the FFN2 dgrad also emits rowdot[row][f-tile] = sum dU (U - b1) for the norm2 backward
-            rowdot = torch.empty(B * Kq, f // TILE, device=dev)
-            K.gemm_rms(OT_GEMM_NT, dy2, d, d, mt['rows'][1], m.p(f'blk.{l}.w2'), f * d, d, f, mt['tile_group'], nt,
-                       du, f, mt['rows'][1], aux=u, ldaux=f, a_xform=OT_AX_BF16 if dy_bf else 0,
-                       epi=OT_EPI_GELU_BWD | OT_EPI_ROWDOT | cbf | (OT_EPI_AUX_BF16 if u.dtype == torch.int16 else 0),
-                       bias=m.p(f'blk.{l}.b1'), bias_gstride=f, rowdot=rowdot, rowdot_n=f // TILE,
-                       m_rows=maps['tail'].nrows, device=dev, bimg=m.bimg(f'blk.{l}.w2', 'dgrad'),
-                       gelu_out=hbf, ldgelu=f, **rep_du, **pa2)
-            if hbf is not None:
-                with m.side(hbf, dy2):
-                    K.wgrad(hbf, f, mt['rows'][1], dy2, d, mt['rows'][1], f, d, mt, nct, G, m.g(f'blk.{l}.w2'),
-                            f * d, m.g(f'blk.{l}.b2'), d, a_xform=OT_AX_BF16, accumulate=acc, device=dev,
-                            m_rows=maps['tail'].nrows, rowmap=maps['tail'])
-        else:
-            K.gemm_rms(OT_GEMM_NT, dy2, d, d, mt['rows'][1], m.p(f'blk.{l}.w2'), f * d, d, f, mt['tile_group'], nt, du,
-                       f, mt['rows'][1], epi=OT_EPI_GELU_BWD, aux=u, ldaux=f, m_rows=maps['tail'].nrows, device=dev,
-                       bimg=m.bimg(f'blk.{l}.w2', 'dgrad'), **rep_du, **pa2)
-        pa1 = a_row_bounds(pw1, du, f, B * Kq, f, rm_du) if not ffn_bwd else {}
-        a1n = x1n is not None and du_bf               # both operands bf16: the copy-staged weight gradient
-        with m.side(x1n if a1n else x1, du, rstd2, *keep):
-            K.wgrad(x1n if a1n else x1, d, mt['rows'][1], du, f, mt['rows'][1], d, f, mt, nct, G, m.g(f'blk.{l}.w1'),
-                    d * f, m.g(f'blk.{l}.b1'), f, rstd=rstd2, gamma=m.p(f'blk.{l}.norm2'),
-                    a_xform=(OT_AX_BF16 if a1n else OT_AX_RMSNORM) | (OT_WG_D_BF16 if du_bf else 0),
-                    accumulate=acc, device=dev, m_rows=maps['tail'].nrows, rowmap=maps['tail'], d_bound=b_du)
-        # FFN1 dgrad -> norm2 backward + residual; emit mask(dx1) for the attention branch
-        dx1_ep = m.fuse_bwd or rowdot is not None   # FFN1 dgrad -> norm2 backward in the epilogue, which reports on dyo
-        if not ffn_bwd:
-            dx1 = torch.empty(B * Kq, d, device=dev)
-            dyo = torch.empty(B * Kq, d, device=dev) if rate > 0 else dx1
-            rm_dyo = torch.empty(B * Kq, (d + TILE - 1) // TILE, device=dev) if pwo and dx1_ep else None
-            b_dyo = out('dyo') if dx1_ep else None
-        if ffn_bwd:
-            pass                                    # dx1 / dyo and their reports came from the fused launch above
-        elif dx1_ep:
-            K.gemm_rms(OT_GEMM_NT, du, f, f, mt['rows'][1], m.p(f'blk.{l}.w1'), d * f, f, d, mt['tile_group'], nt,
-                       dx1, d, mt['rows'][1], epi=OT_EPI_RMSNORM_BWD | (OT_EPI_DROPOUT if rate > 0 else 0),
-                       a_xform=OT_AX_BF16 if du_bf else 0,
-                       seed=seed, site=2 * l, drop=rate, tail=tail, m_rows=maps['tail'].nrows, nx=x1, ldnx=d,
-                       ngamma=m.p(f'blk.{l}.norm2'), nrstd=rstd2, dres=dx2, lddres=d,
-                       dx_masked=dyo if rate > 0 else None, lddxm=d, dgamma=m.g(f'blk.{l}.norm2'),
-                       accumulate_dgamma=acc, device=dev, bimg=m.bimg(f'blk.{l}.w1', 'dgrad'),
-                       rowdot=rowdot, rowdot_n=f // TILE if rowdot is not None else 0, amax_out=b_dyo,
-                       rowabs_out=rm_dyo, rowabs_n=rm_dyo.shape[1] if rm_dyo is not None else 0, **pa1)
-        else:
-            dxn2 = torch.empty(B * Kq, d, device=dev)
-            K.gemm_rms(OT_GEMM_NT, du, f, f, mt['rows'][1], m.p(f'blk.{l}.w1'), d * f, f, d, mt['tile_group'], nt,
-                       dxn2, d, mt['rows'][1], epi=0, m_rows=maps['tail'].nrows, device=dev,
-                       bimg=m.bimg(f'blk.{l}.w1', 'dgrad'), **pa1)
-            K.rmsnorm_bwd(dxn2, d, x1, d, m.p(f'blk.{l}.norm2'), rstd2, dx1, d, B * Kq, d, dres=dx2, lddres=d,
-                          dx_masked=dyo if rate > 0 else None, lddxm=d, seed=seed, site=2 * l, drop=rate,
-                          tail=tail, dgamma=m.g(f'blk.{l}.norm2'), accumulate=acc, device=dev)
-        # Wo
-        with m.side(o, dyo, *keep):
-            _wgrad_single(m, o, dyo, d, d, mt, m.g(f'blk.{l}.wo'), acc, dev, maps['tail'].nrows, maps['tail'],
-                          a_bound=b_o, d_bound=b_dyo)
-        do = torch.empty(B * Kq, d, device=dev)
-        K.gemm_rms(OT_GEMM_NT, dyo, d, d, mt['rows'][1], m.p(f'blk.{l}.wo'), 0, d, d, mt['tile_group'], nt, do, d,
-                   mt['rows'][1], epi=0, m_rows=maps['tail'].nrows, device=dev, bimg=m.bimg(f'blk.{l}.wo', 'dgrad'),
-                   **a_row_bounds(pwo, dyo, d, B * Kq, d, rm_dyo))   # (a row-wise norm backward reports no maxima)
-        if yf is not None:     # the forward took the folded one-query attention
-            dx = _fold_backward(m, l, x, rstd1, qkv, o, lse, yf, do, dx1, B, I, maps['fold'], acc, dev)
-            m.side_block_done()
-            if m.grad_ready is not None:
-                m.grad_ready(l)
-            return None, dx, None, None, None, None, None, None, None, None, None, None
-        # attention
-        # bf16 mode, key-grouped backward (C5): dQKV in bf16 (OT_ATTN_DQKV_BF16) — the QKV dgrad (bf16 A) and
-        # the Wqkv weight gradient (OT_WG_D_BF16) round it to bf16 anyway: the same values, half the bytes
-        qp = _attn_qpos(cfg, pos)
-        dq_bf = (K.matmul_mode() == 'bf16'
-                 and K.attn_bwd_bf16_forms(I, Kq, hd, qp) & _lib.OT_ATTN_DQKV_BF16
-                 and m.bimg(f'blk.{l}.wqkv', 'dgrad') is not None)
-        dqkv = torch.empty(B * I, 3 * d, device=dev, dtype=torch.int16 if dq_bf else torch.float32)
-        if Kq < I:
-            dqkv[:, :d].zero_()
-        bwd_b = kvalid is None and not dq_bf and K.attn_amax_supported(I, Kq, hd, qp, backward=True)
-        b_dq = out('dqkv') if bwd_b else None
-        # the QKV dgrad on the fp16 pair: dQKV's row maxima [row][q / k / v][head] from the attention backward (the
-        # dQ part of rows without a query stays 0), else the row-absmax pass
-        pqkv = m.dgrad_pair(f'blk.{l}.wqkv')
-        rm_dq = torch.zeros(B * I, 3 * H, device=dev) if pqkv and bwd_b else None
-        if kvalid is not None:
-            K.attn_bwd_masked(qkv, 3 * d, o, do, lse, B, H, I, Kq, hd, dqkv, _layer_valid(kvalid, I), qpos=qp)
-        else:
-            K.attn_bwd(qkv, 3 * d, o, do, lse, B, H, I, Kq, hd, dqkv, qpos=qp, dq_part_bf16=True, amax=b_dq,
-                       rowmax=rm_dq)
-        pa_q = a_row_bounds(pqkv, dqkv, 3 * d, B * I, 3 * d, rm_dq)
-        an1 = xn1 is not None and dq_bf
-        with m.side(xn1 if an1 else x, dqkv, rstd1, *keep):
-            K.wgrad(xn1 if an1 else x, d, ma['rows'][0], dqkv, 3 * d, ma['rows'][0], d, 3 * d, ma, nca, G,
-                    m.g(f'blk.{l}.wqkv'), 3 * d * d, None, 0,
-                    a_xform=(OT_AX_BF16 if an1 else OT_AX_RMSNORM) | (OT_WG_D_BF16 if dq_bf else 0), rstd=rstd1,
-                    gamma=m.p(f'blk.{l}.norm1'), accumulate=acc, device=dev, m_rows=maps['all'].nrows,
-                    rowmap=maps['all'], d_bound=b_dq)
-        ax_dq = OT_AX_BF16 if dq_bf else 0
-        dx = torch.empty(B * I, d, device=dev)
-        # the block below masks dx inside its fused FFN backward: this launch reports dx's row maxima and bound
-        rep_dx = {}
-        if pqkv and bwd_mask_gate(m, l - 1, rate, bounds, None):
-            rm_dx = torch.empty(B * I, 1, device=dev)
-            rep_dx = dict(amax_out=out('dx'), rowabs_out=rm_dx, rowabs_n=1)
-        if m.fuse_bwd:         # QKV dgrad -> norm1 backward + residual (dx1 on the kept tail rows)
-            K.gemm_rms(OT_GEMM_NT, dqkv, 3 * d, 3 * d, ma['rows'][0], m.p(f'blk.{l}.wqkv'), 3 * d * d, 3 * d, d,
-                       ma['tile_group'], na, dx, d, ma['rows'][0], epi=OT_EPI_RMSNORM_BWD, a_xform=ax_dq,
-                       m_rows=maps['all'].nrows, nx=x, ldnx=d, ngamma=m.p(f'blk.{l}.norm1'), nrstd=rstd1,
-                       dres=dx1, lddres=d, dres_tail=(Kq, I, inv) if Kq < I else (0, 0),
-                       dgamma=m.g(f'blk.{l}.norm1'), accumulate_dgamma=acc, device=dev,
-                       bimg=m.bimg(f'blk.{l}.wqkv', 'dgrad'), **pa_q, **rep_dx)
-            if rep_dx:
-                bounds.put_dx(l, dx, rm_dx)
-        else:
-            dxn1 = torch.empty(B * I, d, device=dev)
-            K.gemm_rms(OT_GEMM_NT, dqkv, 3 * d, 3 * d, ma['rows'][0], m.p(f'blk.{l}.wqkv'), 3 * d * d, 3 * d, d,
-                       ma['tile_group'], na, dxn1, d, ma['rows'][0], epi=0, m_rows=maps['all'].nrows, a_xform=ax_dq,
-                       bimg=m.bimg(f'blk.{l}.wqkv', 'dgrad'), device=dev, **pa_q)
-            K.rmsnorm_bwd(dxn1, d, x, d, m.p(f'blk.{l}.norm1'), rstd1, dx, d, B * I, d, dres=dx1, lddres=d,
-                          dres_tail=(Kq, I, inv) if Kq < I else (0, 0), dgamma=m.g(f'blk.{l}.norm1'), accumulate=acc,
-                          device=dev)
-        m.side_block_done()
-        if m.grad_ready is not None:
-            m.grad_ready(l)                     # this block's banks are final: the DP exchange may start
-        return None, dx, None, None, None, None, None, None, None, None, None, None
-
-
-def _fold_backward(m, l, x, rstd1, qkv, o, lse, yf, do, dx1, B, I, fmap, acc, dev):
-    """Backward of the folded one-query attention and of the QKV projection around it (``fold_gate``): the fold
-    kernel streams x once and writes dx of every row (norm1's backward applied; + dx1 on the query row); dQKV exists
-    only for the ``fold`` map's rows (the dedicated keys and the query), compact, and the QKV dgrad adds their part
-    onto the dx rows in place; the Wqkv weight gradient runs over those rows, and group 0's dWk / dWv — the keys that
-    were never projected — come from z / y (ot_attn_fold_dw).  No PairBounds slots: these few-thousand-row weight
-    gradients run the exact split.  Returns dx [B*I, d]."""
-    cfg = m.config
-    d, H, G = cfg.hidden_dim, cfg.num_heads, cfg.num_groups
-    hd = d // H
-    ded = m.fold_ded(I)
-    mf = fmap.to(dev)
-    nf = K.attn_fold_rows(I, *ded)
-    g1, w = m.p(f'blk.{l}.norm1'), m.p(f'blk.{l}.wqkv')
-    dqkv = torch.empty(B * nf, 3 * d, device=dev)
-    dx = torch.empty(B * I, d, device=dev)
-    zf = torch.empty(B * H, d, device=dev)
-    dgp = torch.empty(B, d, device=dev)
-    K.attn_fold_bwd(x, d, rstd1, g1, w, 3 * d, m.pT(f'blk.{l}.wqkv'), d, qkv, 3 * d, B, H, I, hd, ded, o, do, lse, yf,
-                    dx1, dx, d, dqkv, 3 * d, zf, dgp)
-    pa_q = a_row_bounds(m.dgrad_pair(f'blk.{l}.wqkv'), dqkv, 3 * d, B * nf, 3 * d)
-    K.gemm_rms(OT_GEMM_NT, dqkv, 3 * d, 3 * d, mf['rows'][1], w, 3 * d * d, 3 * d, d, mf['tile_group'], fmap.ntiles,
-               dx, d, mf['rows'][0], epi=OT_EPI_RMSNORM_BWD, m_rows=fmap.nrows, nx=x, ldnx=d, ngamma=g1, nrstd=rstd1,
-               dres=dx, lddres=d, dgamma=m.g(f'blk.{l}.norm1'), accumulate_dgamma=acc, device=dev,
-               bimg=m.bimg(f'blk.{l}.wqkv', 'dgrad'), **pa_q)
-    K.attn_fold_dgamma(dgp, B, d, m.g(f'blk.{l}.norm1'), accumulate=True)
-    with m.side(x, dqkv, rstd1, zf, yf, qkv, do):
-        K.wgrad(x, d, mf['rows'][0], dqkv, 3 * d, mf['rows'][1], d, 3 * d, mf, fmap.chunks.shape[0], G,
-                m.g(f'blk.{l}.wqkv'), 3 * d * d, None, 0, a_xform=OT_AX_RMSNORM, rstd=rstd1, gamma=g1, accumulate=acc,
-                device=dev, m_rows=fmap.nrows, rowmap=fmap)
-        K.attn_fold_dw(zf, yf, qkv, 3 * d, do, g1, B, H, I, hd, m.g(f'blk.{l}.wqkv'), 3 * d, accumulate=True)
-    return dx
-
-
-def _wgrad_single(m, A, D, K_, N, mt, dW, acc, dev, mrows=0, rowmap=None, a_bound=None, d_bound=None):
-    """Wo gradient: one weight shared by every group -> wgrad with every chunk mapped to group 0
-    (chunked by layout.wgrad_slots for its single output tile when the row map is given)."""
-    if rowmap is not None and rowmap.group_rows:
-        ch, _, _ = rowmap.chunks_for(((K_ + 127) // 128) * ((N + 127) // 128), dev)
-        mp = m.single_group_chunks({'chunks': ch})
-    else:
-        mp = m.single_group_chunks(mt)
-    K.wgrad(A, K_, mt['rows'][1], D, N, mt['rows'][1], K_, N, mp, mp['chunks'].shape[0], 1, dW, 0, None, 0,
-            accumulate=acc, device=dev, m_rows=mrows, a_bound=a_bound, d_bound=d_bound)
-
-
 class _Head(torch.autograd.Function):
     """output_norm + task heads on the last token (model.py:384-391): x [B, d] -> probs [T, B]."""
 
@@ -858,133 +243,6 @@ class _Head(torch.autograd.Function):
         if m.grad_ready is not None:
             m.grad_ready('head')                # out_norm + heads are final: the DP exchange may start
         return None, dx, None
-
-
-class _TaskLoss(torch.autograd.Function):
-    """Σ_task loss (train.py:78-93, 124-128) of the model's heads as the reference's Keras 2.12 computes it:
-    the sigmoid heads' cached logits give tf.nn.sigmoid_cross_entropy_with_logits for 'ctr' / 'cvr' (no
-    clipping), MeanSquaredError on the probabilities for any other task; the gradient goes to the logits."""
-
-    @staticmethod
-    def forward(ctx, probs, logits, labels, mse_mask):
-        T, B = probs.shape
-        loss = torch.empty(1, device=probs.device)
-        K.task_loss_logits_fwd(logits, probs, labels, T, B, loss, device=probs.device, mse_mask=mse_mask)
-        ctx.save_for_backward(probs, labels)
-        ctx.mse_mask = mse_mask
-        return loss[0]
-
-    @staticmethod
-    def backward(ctx, gl):
-        probs, labels = ctx.saved_tensors
-        T, B = probs.shape
-        dlogits = torch.empty_like(probs)
-        gl = gl.reshape(1).contiguous().float()
-        K.task_loss_logits_bwd(probs, labels, gl, T, B, dlogits, mse_mask=ctx.mse_mask)
-        return None, dlogits, None, None
-
-
-class _BCE(torch.autograd.Function):
-    """Σ_task loss (train.py:78-93, 124-128) on probs [T, B]: tf.keras BinaryCrossentropy for 'ctr' /
-    'cvr', MeanSquaredError for any other task (bit t of ``mse_mask``)."""
-
-    @staticmethod
-    def forward(ctx, probs, labels, mse_mask):
-        T, B = probs.shape
-        loss = torch.empty(1, device=probs.device)
-        K.bce_fwd(probs, labels, T, B, loss, device=probs.device, mse_mask=mse_mask)
-        ctx.save_for_backward(probs, labels)
-        ctx.mse_mask = mse_mask
-        return loss[0]
-
-    @staticmethod
-    def backward(ctx, gl):
-        probs, labels = ctx.saved_tensors
-        T, B = probs.shape
-        dprobs = torch.empty_like(probs)
-        gl = gl.reshape(1).contiguous().float()
-        K.bce_bwd(probs, labels, gl, T, B, dprobs, mse_mask=ctx.mse_mask)
-        return dprobs, None, None
-
-
-class _WeightedTaskLoss(torch.autograd.Function):
-    """Σ_t a_t (Σ_b w l) / denom_t: the per-element terms of ``_TaskLoss`` (``logits`` given: the
-    gradient goes to the logits) or of ``_BCE`` (``logits`` None: to the probabilities) under per-(task, sample)
-    weights.  The forward leaves the denominators on the device for the backward: no host sync."""
-
-    @staticmethod
-    def forward(ctx, probs, logits, labels, weights, wstride, task_scale, mse_mask, reduction):
-        T, B = probs.shape
-        loss = torch.empty(1, device=probs.device)
-        denom = torch.empty(T, device=probs.device)
-        K.task_loss_weighted_fwd(logits, probs, labels, weights, wstride, task_scale, T, B, loss, denom,
-                                 device=probs.device, mse_mask=mse_mask, reduction=reduction)
-        ctx.save_for_backward(probs, labels, weights, denom, task_scale)
-        ctx.args = (wstride, mse_mask, logits is None)
-        return loss[0]
-
-    @staticmethod
-    def backward(ctx, gl):
-        probs, labels, weights, denom, task_scale = ctx.saved_tensors
-        wstride, mse_mask, prob_form = ctx.args
-        T, B = probs.shape
-        dout = torch.empty_like(probs)
-        gl = gl.reshape(1).contiguous().float()
-        K.task_loss_weighted_bwd(probs, labels, weights, wstride, task_scale, denom, gl, T, B, dout,
-                                 mse_mask=mse_mask, prob_form=prob_form)
-        return (dout, None) + (None,) * 6 if prob_form else (None, dout) + (None,) * 6
-
-
-BINARY_TASKS = ('ctr', 'cvr')      # train.py:83: BCE for these, MSE for every other task
-
-
-def task_mse_mask(tasks) -> int:
-    """Bit t set when task t trains with MeanSquaredError (train.py:88-91)."""
-    if len(tasks) > 32:
-        raise ValueError('at most 32 tasks')
-    return sum(1 << i for i, t in enumerate(tasks) if t not in BINARY_TASKS)
-
-
-def keras_bce_loss(labels: torch.Tensor, probs: torch.Tensor, tasks=None, label_rank: int = 2, weights=None,
-                   task_scale=None, reduction: str = 'batch') -> torch.Tensor:
-    """Sum over tasks of the reference's per-task loss; labels/probs [T, B] device tensors.  ``tasks``
-    (names, in row order) selects MSE for tasks other than 'ctr'/'cvr'; None = BCE for every row.
-    Probabilities from ``OneTransModel.forward_probs`` carry their heads' logits (``_ot_logits``, as Keras's
-    sigmoid output carries ``_keras_logits``) and the BCE is taken from those when the caller's labels were
-    [B, 1] (``label_rank`` 2: create_sample_batch, data_loader.py:327).  Keras 2.12 squeezes the [B, 1]
-    prediction to [B] for [B] labels (get_tf_dataset's batched scalars, data_loader.py:215-218), which drops
-    the cached logits: ``label_rank`` 1 and probabilities without logits use the clipped probability form.
-
-    ``weights`` (float32 device tensor: [T, B], or [B] / [1, B] shared by the tasks; values in [0, 65536], a zero
-    removes the entry whatever its label holds), ``task_scale`` (T coefficients a_t: a sequence or a device tensor)
-    and ``reduction`` ('batch': Σ_t a_t Σ_b w l / B, Keras's SUM_OVER_BATCH_SIZE with ``sample_weight``; 'weights':
-    ... / Σ_b w) select the weighted loss (DESIGN.md §7h).  With ``weights`` None the call is the un-weighted one;
-    ``task_scale`` / ``reduction`` then need weights (pass ones)."""
-    mask = task_mse_mask(tasks) if tasks is not None else 0
-    z = getattr(probs, '_ot_logits', None) if label_rank >= 2 else None
-    if weights is None and (task_scale is not None or reduction != 'batch'):
-        raise ValueError('keras_bce_loss: task_scale / reduction apply to the weighted loss; pass weights')
-    if weights is not None:
-        T, B = probs.shape
-        if reduction not in _lib.LOSS_REDUCTIONS:
-            raise ValueError(f"unknown reduction {reduction!r}: expected 'batch' or 'weights'")
-        if weights.dtype != torch.float32 or weights.device != probs.device:
-            raise ValueError('keras_bce_loss: weights must be a float32 tensor on the device of probs')
-        if weights.dim() == 2 and tuple(weights.shape) == (T, B) and T > 1:
-            # (an expanded [1, B] row stays one row: weight stride 0)
-            weights, wstride = (weights[0].contiguous(), 0) if weights.stride(0) == 0 else (weights.contiguous(), B)
-        elif weights.numel() == B:
-            weights, wstride = weights.reshape(-1).contiguous(), 0
-        else:
-            raise ValueError(f'keras_bce_loss: weights of shape {tuple(weights.shape)}; expected [{T}, {B}] or [{B}]')
-        if task_scale is not None and not isinstance(task_scale, torch.Tensor):
-            task_scale = torch.tensor([float(a) for a in task_scale], dtype=torch.float32, device=probs.device)
-        if task_scale is not None and (task_scale.numel() != T or task_scale.dtype != torch.float32):
-            raise ValueError(f'keras_bce_loss: task_scale must hold {T} float32 coefficients')
-        return _WeightedTaskLoss.apply(probs, z, labels, weights, wstride, task_scale, mask, reduction)
-    if z is not None:
-        return _TaskLoss.apply(probs, z, labels, mask)
-    return _BCE.apply(probs, labels, mask)
 
 
 # =============================================================================== the module
@@ -1341,12 +599,12 @@ class OneTransModel(nn.Module):
             self._aux_maps[key] = run if ded == list(range(*run)) else None
         return self._aux_maps[key]
 
-    def fold_gate(self, I: int, Kq: int, select: bool, kvalid):
+    def fold_gate(self, I: int, Kq: int, select: bool, masked: bool):
         """Does a block of I tokens keeping Kq take the folded one-query attention?  Its dedicated
         range (``fold_ded``) when it does, else None: the block then runs the K/V projection of every row and the
         attention kernels, exactly as without the switch (ONETRANS_LAST_FOLD / K.last_fold)."""
         cfg = self.config
-        if (Kq != 1 or I < 2 or select or kvalid is not None or self.attn_fp8 or not self.fuse_bwd
+        if (Kq != 1 or I < 2 or select or masked or self.attn_fp8 or not self.fuse_bwd
                 or K.matmul_mode() not in ('split', 'f32') or not K.last_fold()
                 or not K.attn_fold_supported(cfg.hidden_dim, cfg.num_heads)):
             return None

@@ -28,7 +28,8 @@ import torch
 
 from . import kernels as K
 from ._lib import OT_AX_GELU, OT_AX_RMSNORM, OT_EPI_GELU_BWD, OT_GEMM_NT
-from .model import _Head, _Tokenize, _wgrad_single, layer_seed
+from .block import _wgrad_single, layer_seed
+from .model import _Head, _Tokenize
 from .span_block import check_req, request_schedule, s_rows, s_rows_grad, span_forward
 
 N_SEED_OFFSET = 0x632BE5AB        # odd: the N span's dropout seed is the layer seed plus this (mod 2^32)

@@ -11,7 +11,7 @@ import torch
 
 from . import kernels as K
 from ._lib import OT_AX_GELU, OT_AX_RMSNORM, OT_EPI_BIAS, OT_EPI_DROPOUT, OT_EPI_RESIDUAL, OT_GEMM_NT
-from .model import RMS_EPS
+from .block import RMS_EPS
 
 
 def request_schedule(cfg, L_S: int) -> List[Dict]:

@@ -27,8 +27,9 @@ from . import dist as otdist
 from . import kernels as K
 from .config import (LOSS_WEIGHT_MAX, OneTransConfig, dense_optimizer_spec, get_model_config, sparse_optimizer_spec,
                      task_loss_scale)
+from .loss import BINARY_TASKS, keras_bce_loss
 from .metrics import GroupedAUC, StreamingMetrics, auc, div_no_nan, keras_auc
-from .model import BINARY_TASKS, OneTransModel, keras_bce_loss
+from .model import OneTransModel
 
 
 def _to_dev(d: Dict, dev) -> Dict[str, torch.Tensor]:
