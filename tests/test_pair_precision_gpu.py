@@ -26,6 +26,8 @@ from recommend_amd import kernels as K
 from recommend_amd._lib import (OT_AX_GELU, OT_AX_RMSNORM, OT_EPI_BIAS, OT_EPI_RESIDUAL, OT_GEMM_NT)
 from recommend_amd.layout import IMAGE_UNIT_ELEMS, build_map
 
+import attn_edges_ref as AE
+
 PAIR_VS_F32 = 4.0
 EPS = 1e-6
 
@@ -288,6 +290,15 @@ def test_pair_slice_attention(dev, B, H, I, Kq, hd, case):
                 ref.abs().max().item())
     check_ratio(f'attn bwd B{B} I{I} K{Kq} hd{hd} {case}', errs(gp, qr.grad), errs(gf, qr.grad),
                 qr.grad.abs().max().item())
+    # the f32 kernels are this test's yardstick: pin them to the same operation evaluated in float32 on the CPU, so
+    # the two kernel families cannot be wrong together (tests/attn_edges_ref.py: the margin of the f32 kernels)
+    qpos = AE.tail_qpos(B, I, Kq)
+    cpu32 = AE.evaluate(lambda x: AE.plain(x, B, H, I, hd, qpos), [qkv], dout, torch.float32)
+    for name, got, want, y in [('fwd', of, ref.detach(), cpu32['out']), ('bwd', gf, qr.grad, cpu32['grads'][0])]:
+        e_k, e_y = errs(got, want), AE.err(y, want)
+        print(f'attn {name} B{B} I{I} K{Kq} hd{hd} {case}: f32 kernel {e_k:.3e}  CPU float32 {e_y:.3e}')
+        assert e_k <= AE.bound(e_y, want, AE.MARGIN_F32), \
+            f'attn {name}: f32 kernel error {e_k:.3e} > {AE.MARGIN_F32} x CPU float32 {e_y:.3e}'
 
 
 @pytest.mark.parametrize('K_,N', [(128, 384), (128, 512), (512, 128), (256, 1024)])
